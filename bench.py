@@ -1,7 +1,16 @@
 """Benchmark: train mel-frames/sec of the FastSpeech2-with-emotion-intensity train step
 (BASELINE.json metric) at B=32 utterances per GPU, 80-bin mel, default model dims, bf16.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (``metric``,
+``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step`` and the configuration).
+``--dump-outputs DIR`` also writes what the last timed step computed (``dump_outputs``).
+``--full`` adds every other measurement to the line: the roofline kernels' HIP-event times
+(brackets around their launches in the timed steps), and after the timed steps the host enqueue
+time, the train step with the frozen IntensityExtractor, the fp32 and config-2 legs and the CPU
+baseline (``--no-cpu-baseline``, ``--no-extractor``, ``--no-fp32-leg``, ``--no-config2-leg``
+drop single legs of a full run).
 
 N>1: one process per GPU with the nccl (= RCCL) backend.  Under torch.distributed.run (the
 driver's launch: WORLD_SIZE/RANK/LOCAL_RANK in the environment) WORLD_SIZE must equal --gpus.
@@ -83,6 +92,11 @@ def parse(argv=None):
                          "the world size and the ranks seen; no GPU is touched")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: roofline kernel "
+                         "times, host enqueue time, extractor / fp32 / config-2 legs, CPU baseline")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--max-shape", action="store_true", help="all T_phon=200, d=5 (T_mel=1000)")
@@ -307,6 +321,33 @@ def extractor_leg(cfg_all, args, trainer, b, bt, Tm, dt, world, frames_local):
                     "(train.py:69-81); extractor weights random-init, rank_X from the batch"}
 
 
+DUMP_SAMPLE = 4 << 20     # elements kept of the flat parameter buffer: 16 MiB as float32
+
+
+def dump_outputs(out_dir, loss, model):
+    """--dump-outputs: what the last timed step left with its caller, as float32 .npy files.
+    ``loss`` is the step's return value (the loss vector).  The step also updates the model in
+    place, so ``params`` is the flat parameter buffer after it: 85 M floats, of which DUMP_SAMPLE
+    fixed positions are kept (a seeded draw that depends on the buffer length alone, in
+    ascending order).  Call after a synchronize and before any further step.
+
+    The inputs, initial weights and dropout seeds of a run are fixed by its arguments; the
+    outputs still differ between two runs of one build at rounding level, because the split-K
+    weight gradients are summed by fp32 atomics in varying order and AdamW carries that through
+    the steps: a parameter whose gradient is near zero can move by the learning rate (1e-4)
+    either way in each step (measured in bf16 with
+    --warmup 5: loss 2e-5 relative; parameters 9e-4 absolute after --steps 20, 2.4e-3 after
+    --steps 50, against a largest parameter of 3.8)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().cpu().numpy())
+    flat = model._flat
+    if flat.numel() > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), size=DUMP_SAMPLE))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    np.save(os.path.join(out_dir, "params.npy"), flat.detach().float().cpu().numpy())
+
+
 def plumbing_check(world, rank, local):
     """--plumbing-check: the rank environment the launcher produced, gathered over gloo."""
     if world > 1:
@@ -383,12 +424,16 @@ def main():
     torch.cuda.synchronize()
     timer = KernelTimer()
     timer.detail = args.detail
-    # FS2_BENCH_NO_TIMER=1 (A/B runs): no HIP-event brackets in the timed region
-    trainer.eng.timer = None if os.environ.get("FS2_BENCH_NO_TIMER") else timer
+    # the HIP-event brackets of the roofline kernels belong to --full (and --detail); without
+    # them, or with FS2_BENCH_NO_TIMER=1 (A/B runs), the timed region holds the steps alone
+    bracketed = (args.full or args.detail) and not os.environ.get("FS2_BENCH_NO_TIMER")
+    trainer.eng.timer = timer if bracketed else None
+    # one more untimed step counts the brackets; their events are created before t0.  It runs
+    # without brackets too, so that the timed steps (dropout seeds, optimizer state) and with
+    # them --dump-outputs are the same with and without --full
+    trainer.step(bt, inten, mel_len_max=Tm)
+    torch.cuda.synchronize()
     if trainer.eng.timer is not None:
-        # one more untimed step counts the brackets; their events are created before t0
-        trainer.step(bt, inten, mel_len_max=Tm)
-        torch.cuda.synchronize()
         n_ev = timer.n_events()
         timer.reset()
         timer.reserve(n_ev * args.steps)
@@ -403,9 +448,12 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     trainer.eng.timer = None
+    loss_v = loss.float().cpu().tolist()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, model)
     ks = timer.summary()
     graphed = trainer.use_graph
-    if graphed:
+    if graphed and args.full:
         # a graph replay runs the captured launches without the host-side HIP-event brackets:
         # time the roofline kernel in an eager pass of the same step (same kernels, arguments
         # and inputs), on the stream the kernel is launched on
@@ -421,12 +469,14 @@ def main():
     # host time to issue one step's launches, from an idle queue: 3 steps enqueued right after
     # a synchronize (inside the timed loop the host runs ~10 steps ahead of the GPU and then
     # blocks on the HIP queue's back-pressure, which made "host time" track the GPU's)
-    torch.cuda.synchronize()
-    h0 = time.perf_counter()
-    for _ in range(3):
-        trainer.step(bt, inten, mel_len_max=Tm)
-    host_enqueue = (time.perf_counter() - h0) / 3
-    torch.cuda.synchronize()
+    host_enqueue = None
+    if args.full:
+        torch.cuda.synchronize()
+        h0 = time.perf_counter()
+        for _ in range(3):
+            trainer.step(bt, inten, mel_len_max=Tm)
+        host_enqueue = (time.perf_counter() - h0) / 3
+        torch.cuda.synchronize()
     if args.detail and rank == 0:
         detail_table(ks, trainer.eng, args.batch, args.steps, elapsed)
     tmax = torch.tensor([elapsed], device="cuda")
@@ -436,11 +486,10 @@ def main():
         dist.all_reduce(ftot, op=dist.ReduceOp.SUM)
     elapsed = float(tmax.item())
     frames_all = float(ftot.item())
-    loss_v = loss.float().cpu().tolist()
     ext_info = None
-    if not args.no_extractor:
+    if args.full and not args.no_extractor:
         ext_info = extractor_leg(cfg_all, args, trainer, b, bt, Tm, dt, world, frames_local)
-    legs = secondary_legs(cfg_all, args, rank, world)
+    legs = secondary_legs(cfg_all, args, rank, world) if args.full else {}
     if rank == 0:
         c = model.cfg
         D, F, KW = c.dec_d_model, c.dec_ffn_dim, c.ffn_cnn_kernel_size_list[0]
@@ -513,14 +562,18 @@ def main():
                               "definition": "SURVEY 8(d): frames/s x train FLOP per mel frame "
                                             "(fwd + 2x bwd at T_phon=200, T_mel=1000) / peak"},
             "step_mfma_frac": step_tflops / (MFMA_BF16_PEAK_TFLOPS * world),
-            "host_enqueue_ms_per_step": host_enqueue * 1e3,
+            "host_enqueue_ms_per_step": None if host_enqueue is None else host_enqueue * 1e3,
             "kernel_ms": {k: v[1] for k, v in ks.items()},
             "loss_total_last": loss_v[0],
         }
+        if not args.full:
+            # measured by --full alone: a plain line does not carry their empty entries
+            for k in ("roofline", "roofline_conv1_wgrad", "host_enqueue_ms_per_step", "kernel_ms"):
+                del line[k]
         if ext_info is not None:
             line["with_intensity_extractor"] = ext_info
         line.update(legs)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(cfg_all, args)
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -4,7 +4,9 @@
   refusal to measure fewer devices than asked;
 * end to end: ``bench.py --gpus 2 --plumbing-check`` started without a launcher re-runs itself
   under torch.distributed.run and each rank sees RANK / LOCAL_RANK / WORLD_SIZE (gloo, no GPU);
-* ``bench.py --gpus 2`` on a box with fewer GPUs exits non-zero instead of measuring one.
+* ``bench.py --gpus 2`` on a box with fewer GPUs exits non-zero instead of measuring one;
+* ``--dump-outputs`` / ``--full``: what a dump holds, and (GPU) that a plain run prints the
+  headline fields alone.
 """
 import json
 import os
@@ -104,3 +106,63 @@ def test_bench_two_rank_path_rehearsed_on_one_gpu():
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 64
     assert d["config"]["parallelism"] == "dp2" and "rehearsal" in d
     assert d["value"] > 0 and d["build"]["library_source_hash"] == d["build"]["tree_source_hash"]
+
+
+def test_dump_outputs_writes_float32_arrays_at_fixed_positions(tmp_path, monkeypatch):
+    """--dump-outputs: loss and params as float32 .npy; a flat buffer longer than DUMP_SAMPLE is
+    sampled at positions that depend on its length alone, a shorter one is written whole."""
+    import types
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    loss = torch.arange(7, dtype=torch.bfloat16)
+    got = {}
+    for d, n in (("a", 4099), ("b", 4099), ("small", 1000)):
+        m = types.SimpleNamespace(_flat=torch.arange(n, dtype=torch.float32))
+        bench.dump_outputs(str(tmp_path / d), loss, m)
+        assert sorted(os.listdir(tmp_path / d)) == ["loss.npy", "params.npy"]
+        got[d] = {k: np.load(tmp_path / d / f"{k}.npy") for k in ("loss", "params")}
+        assert all(v.dtype == np.float32 for v in got[d].values())
+        assert np.array_equal(got[d]["loss"], np.arange(7, dtype=np.float32))
+    p = got["a"]["params"]                                             # values = positions
+    assert p.shape == (1000,) and np.all(np.diff(p) >= 0) and p[0] >= 0 and p[-1] < 4099
+    assert len(np.unique(p)) > 800                                     # spread over the buffer
+    assert np.array_equal(p, got["b"]["params"])
+    assert np.array_equal(got["small"]["params"], np.arange(1000, dtype=np.float32))
+
+
+FULL_ONLY = ("roofline", "roofline_conv1_wgrad", "kernel_ms", "host_enqueue_ms_per_step",
+             "with_intensity_extractor", "fp32", "config2_b16_single_speaker_bf16", "cpu_baseline")
+
+
+def test_full_is_off_by_default():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    assert bench.parse(["--full"]).full is True
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_reports_the_headline_alone_and_dumps_outputs(tmp_path):
+    """GPU: ``bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`` times K steps, prints the
+    headline fields without any --full measurement, and writes the last step's arrays."""
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps",
+                        "2", "--warmup", "1", "--batch", "2", "--dump-outputs", str(tmp_path)],
+                       cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(line) == 1, r.stdout
+    d = json.loads(line[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert d["unit"] == "mel-frames/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert d["metric"].startswith("train mel-frames/sec")
+    frames = d["config"]["valid_mel_frames_per_step"]
+    assert d["ms_per_step"] > 0 and d["value"] == pytest.approx(frames / (d["ms_per_step"] * 1e-3))
+    assert not [k for k in FULL_ONLY if k in d]
+    assert sorted(os.listdir(tmp_path)) == ["loss.npy", "params.npy"]
+    out = {k: np.load(tmp_path / f"{k}.npy") for k in ("loss", "params")}
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in out.values())
+    assert out["loss"].ndim == 1 and out["loss"][0] == pytest.approx(d["loss_total_last"])
+    assert out["params"].shape == (bench.DUMP_SAMPLE,)
+    assert np.count_nonzero(out["params"]) > bench.DUMP_SAMPLE // 2
+    assert sum(v.nbytes for v in out.values()) <= 64 << 20

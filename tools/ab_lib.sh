@@ -4,7 +4,7 @@
 set -o pipefail
 cd ${GRAFT_REPO_ROOT:-$(pwd)}
 L=$(pwd)/fine-grained-emotional-control-of-tts_amd/fastspeech2
-BA="--no-cpu-baseline --no-extractor --no-fp32-leg --no-config2-leg"
+BA="--full --no-cpu-baseline --no-extractor --no-fp32-leg --no-config2-leg"
 for i in $(seq ${1:-3}); do
   FS2_LIB_OTHER_SOURCES=1 FS2_HIP_LIB=$L/libfs2_hip_base.so timeout -k 10 200 python -u bench.py $BA 2>/dev/null > /tmp/abl_A.json || exit 1
   timeout -k 10 200 python -u bench.py $BA 2>/dev/null > /tmp/abl_B.json || exit 1

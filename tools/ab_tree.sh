@@ -7,7 +7,7 @@ R=$(pwd); REPS=${1:-3}
 A=/tmp/ab_A; rm -rf $A; mkdir -p $A
 tar --exclude=./gpurun_out --exclude=./ab_base -cf - . | tar -xf - -C $A
 (cd ab_base && tar -cf - .) | tar -xf - -C $A
-BA="--no-cpu-baseline --no-extractor --no-fp32-leg --no-config2-leg"
+BA="--full --no-cpu-baseline --no-extractor --no-fp32-leg --no-config2-leg"
 for i in $(seq $REPS); do
   for t in A B; do
     d=$R; [ $t = A ] && d=$A
