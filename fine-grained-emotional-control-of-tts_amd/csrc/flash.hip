@@ -5,9 +5,9 @@
 // torch nn.MultiheadAttention as SB calls it (model.py:338-346, 411-427),
 // with the reference's head-major mask tiling: for z = b*H + h the key k is
 // masked iff key_pad[b][k] | key_pad[(b*H + h) % B][k] (mask_mode 1), or with plain key padding
-// key_pad[b][k] (mask_mode 0: the IntensityExtractor's MHA, rank_model/model.py:35).  Dropout on the probabilities uses
-// the same pair hash (fs2_keep_fast) and element index ((z*T + q)*round_up(T, 2) + k) as the
-// materialised path (attention.hip), so both paths draw identical masks.
+// key_pad[b][k] (mask_mode 0: the IntensityExtractor's MHA, rank_model/model.py:35).  Dropout on the probabilities
+// draws fs2_attn_keep(dkey, row = z*T + q, k) (fs2_common.h: a hash per query row, one mix round per
+// key pair), as the materialised path (attention.hip) does, so both paths draw identical masks.
 //
 // Layout: Q, K, V are column blocks of the packed projection QKV [B*T][ldq] (q | k | v, head
 // h at columns h*dh of each block); the context O is [B*T][ldo] with head h at h*dh.
@@ -563,7 +563,8 @@ __global__ void __launch_bounds__(W8 * 64 / QG, 1) attn_fwd_kernel(AttnP p) {
 
 // ------------------------------------------------------------------------------ backward dQ
 // block: 16 * W8 queries = (W8 / QG) waves x QG 16-query groups; also writes D = rowsum(dO * O)
-// and the dropout row hash of every query row (workspace) for the dK/dV kernel
+// and the dropout row hash of every query row (workspace) for the dK/dV kernel (D from the
+// unrounded probabilities where one key tile holds every valid key: see the tile loop)
 template <int DH, int QG, int W8 = 8>
 __global__ void __launch_bounds__(W8 * 64 / QG, 1) attn_bwd_dq_kernel(AttnP p) {
   constexpr int NT = W8 * 64 / QG;
@@ -668,6 +669,37 @@ __global__ void __launch_bounds__(W8 * 64 / QG, 1) attn_bwd_dq_kernel(AttnP p) {
       }
     const bool full = k0 + 64 <= kfull;
     const uint32_t tkc = (uint32_t)(k0 >> 1) * FS2_ATTN_KC;
+    // Every valid key in this one tile: D is taken from the unrounded probabilities.  With
+    // D~ = rowsum(dO * O) of the bf16 O, sum_k P_k (dP_k - D~) = D - D~ (the P_k sum to 1), i.e.
+    // what the rounding of O put into D~; with few valid keys P_k is near 1 and that error
+    // reached dQ / dK whole (one valid key: dS = dP - D~ instead of 0).  Here S and dP of all
+    // the keys are at hand before dS is formed, so the sum costs one more pass over the tile's
+    // registers; rows with more than one key tile keep D~ (the sum would need all tiles first).
+    if (ntile == 1) {
+#pragma unroll
+      for (int qg = 0; qg < QG; ++qg) {
+        float part = 0.f;
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) {
+          const uint32_t kw = full ? 0x01010101u : *(const uint32_t*)(kval + k0 + kt * 16 + 4 * g);
+#pragma unroll
+          for (int e2 = 0; e2 < 2; ++e2) {
+            const uint32_t hh = drop ? fs2_attn_mix(dc[qg][kt][e2] + tkc) : 0u;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+              const int r = 2 * e2 + e;
+              float pr = fexp2(fmaf(sacc[kt][qg][r], c, nlse[qg]));
+              if (!full) pr = (kw >> (8 * r)) & 1u ? pr : 0.f;
+              float dp = pacc[kt][qg][r];
+              if (drop) dp = ((hh >> (16 * e)) & 0xffffu) >= p.thr16 ? dp * p.inv_keep : 0.f;
+              part += pr * (dp - dsum[qg]);
+            }
+          }
+        }
+        dsum[qg] += xg_sum(part);
+        if (qi[qg] < p.T && g == 0) p.dsum[(long)z * p.T + qi[qg]] = dsum[qg];   // for dK/dV
+      }
+    }
     bf16x8 sf[QG][2];
 #pragma unroll
     for (int qg = 0; qg < QG; ++qg) {
@@ -1267,13 +1299,13 @@ void launch_bwd(const AttnP& p, hipStream_t s) {
   // T = 200 with the LDS-DMA dK/dV kernel: 60.2 -> 56.7 us)
   if (attn_small_blocks(p)) {
     dim3 g1((p.T + 63) / 64, p.B * p.H);
-    if (DH <= 64) hipLaunchKernelGGL((attn_bwd_dq_kernel<DH, 2, 4>), g1, dim3(128), 0, s, p);
+    if constexpr (DH <= 64) hipLaunchKernelGGL((attn_bwd_dq_kernel<DH, 2, 4>), g1, dim3(128), 0, s, p);
     else hipLaunchKernelGGL((attn_bwd_dq_kernel<DH, 1, 4>), g1, dim3(256), 0, s, p);
     hipLaunchKernelGGL((attn_bwd_dkv_kernel<DH, 4>), g1, dim3(256), 0, s, p);
     return;
   }
   dim3 g1((p.T + 127) / 128, p.B * p.H);
-  if (DH <= 64) hipLaunchKernelGGL((attn_bwd_dq_kernel<DH, 2>), g1, dim3(256), 0, s, p);
+  if constexpr (DH <= 64) hipLaunchKernelGGL((attn_bwd_dq_kernel<DH, 2>), g1, dim3(256), 0, s, p);
   else hipLaunchKernelGGL((attn_bwd_dq_kernel<DH, 1>), g1, dim3(512), 0, s, p);
   // FS2_ATTN_BWD=4 (experiments build): the paired dK / dV kernel -- bit-identical, 241 -> 235
   // us without dropout but 251 -> 263 us with it (tools/attn_ab_bwd.sh), so off

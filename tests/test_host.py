@@ -79,6 +79,65 @@ def test_gemm_host_validation_rejects_bad_args():
     assert lib.fs2_loss_fwd_bwd(None, None) == -1
 
 
+def test_attention_host_validation_rejects_bad_args():
+    """fs2_attn_fwd / fs2_attn_bwd / fs2_softmax_fwd / fs2_softmax_bwd return before any launch
+    on bad arguments.  Every call here must be refused: one that passed the checks would launch."""
+    from fastspeech2 import _native as N
+    lib = N.load()
+    buf = (ctypes.c_char * 4096)()
+    p16 = (ctypes.addressof(buf) + 15) // 16 * 16
+    good = dict(qkv=p16, ldq=3 * 2 * 64, key_pad=p16, B=2, H=2, T=16, dh=64, out=p16, ldo=128,
+                dout=p16, lddo=128, lse=p16, dqkv=p16, lddq=3 * 2 * 64, ws=p16, dtype=N.BF16)
+
+    def fwd(**bad):
+        a = dict(good, **bad)
+        assert bad, "a call without a fault would launch"
+        return lib.fs2_attn_fwd(a["qkv"], a["ldq"], a["key_pad"], 1, a["B"], a["H"], a["T"],
+                                a["dh"], 0.125, 0.1, 1, 2, a["out"], a["ldo"], a["lse"],
+                                a["dtype"], None)
+
+    def bwd(**bad):
+        a = dict(good, **bad)
+        assert bad, "a call without a fault would launch"
+        return lib.fs2_attn_bwd(a["qkv"], a["ldq"], a["key_pad"], 1, a["out"], a["ldo"], a["dout"],
+                                a["lddo"], a["lse"], a["B"], a["H"], a["T"], a["dh"], 0.125, 0.1,
+                                1, 2, a["dqkv"], a["lddq"], a["ws"], a["dtype"], None)
+
+    for call in (fwd, bwd):
+        assert call(dtype=N.F32) == -1                        # bf16 only
+        assert call(T=0) == -1 and call(T=2049) == -1         # 1 <= T <= 2048
+        assert call(B=0) == -1
+        assert call(dh=96) == -1                              # head sizes 64 / 128 / 192 / 256
+        for name in ("key_pad", "out", "lse"):
+            assert call(**{name: None}) == -1, name
+        assert call(qkv=p16 + 2) == -2                        # misaligned pointer
+        assert call(ldq=3 * 2 * 64 + 4) == -2                 # pitch not 16-byte aligned
+        assert call(ldq=3 * 2 * 64 - 8) == -2                 # pitch below q | k | v
+    assert bwd(ws=None) == -1
+    for name in ("out", "dout", "dqkv"):
+        assert bwd(**{name: p16 + 2}) == -2, name
+    for name in ("ldo", "lddo", "lddq"):
+        assert bwd(**{name: good[name] + 4}) == -2, name
+
+    for dh in (64, 128, 192, 256):
+        assert lib.fs2_attn_supported(2048, dh, N.BF16) == 1
+    assert lib.fs2_attn_supported(2049, 64, N.BF16) == 0
+    assert lib.fs2_attn_supported(2048, 96, N.BF16) == 0
+    assert lib.fs2_attn_supported(2048, 64, N.F32) == 0
+
+    def sm_fwd(B=3, Tk=16, ldt=16, dtype=N.F32):
+        return lib.fs2_softmax_fwd(p16, p16, 1, B, 2, 16, Tk, ldt, 0.5, 0.1, 1, 2, p16, p16,
+                                   dtype, None)
+
+    def sm_bwd(B=3, Tk=16, ldt=16, dtype=N.F32):
+        return lib.fs2_softmax_bwd(p16, p16, B, 2, 16, Tk, ldt, 0.5, 0.1, 1, 2, p16, dtype, None)
+
+    for call in (sm_fwd, sm_bwd):
+        assert call(Tk=17) == -1                              # ldt < Tk
+        assert call(dtype=7) == -1                            # unknown dtype
+        assert call(B=0) == 0                                 # an empty batch is a no-op
+
+
 def test_ctypes_argument_counts_match_header():
     """every prototype in include/fs2_hip.h has as many parameters as its ctypes signature in
     fastspeech2/_native.py (a parameter added on one side only shifts every later argument)"""
