@@ -1052,7 +1052,8 @@ extern "C" int fs2_ln_bwd(const void* dy, int64_t lddy, const void* s, int64_t l
                           float* dcol, int M, int D, int dtype, uint32_t seed, float* workspace,
                           void* stream) {
   if (M <= 0) return 0;
-  if (D <= 0 || D > 64 * MAXJ || !dy || !s || !ds || !gamma || !beta) return FS2_EINVAL;
+  if (D <= 0 || D > 64 * MAXJ || !dy || !s || !ds || !gamma || !beta || !mean || !rstd)
+    return FS2_EINVAL;
   if ((dgamma || dbeta) && (!dgamma || !dbeta)) return FS2_EINVAL;
   if ((dgamma || dcol) && !workspace) return FS2_EINVAL;
   const int nb = ln_blocks(M);

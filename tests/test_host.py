@@ -138,6 +138,63 @@ def test_attention_host_validation_rejects_bad_args():
         assert call(B=0) == 0                                 # an empty batch is a no-op
 
 
+def test_layernorm_host_validation_rejects_bad_args():
+    """fs2_ln_fwd / fs2_ln_bwd / fs2_sum_slices return FS2_EINVAL before any launch on bad
+    arguments, and 0 for an empty problem.  Every other call here must be refused: one that
+    passed the checks would launch."""
+    from fastspeech2 import _native as N
+    lib = N.load()
+    buf = (ctypes.c_char * 4096)()
+    p16 = (ctypes.addressof(buf) + 15) // 16 * 16
+    good = dict(x=p16, y=p16, gamma=p16, beta=p16, mean=p16, rstd=p16, dy=p16, s=p16, ds=p16,
+                dgamma=None, dbeta=None, dcol=None, ws=None, img=None, img_t=0, img_p=0,
+                M=16, D=64, dtype=N.BF16)
+
+    def fwd(**bad):
+        a = dict(good, **bad)
+        assert bad, "a call without a fault would launch"
+        return lib.fs2_ln_fwd(a["x"], a["D"], None, 0, 0.0, 0, None, a["gamma"], a["beta"], 1e-5,
+                              0, 0.1, 3, None, None, 0, a["y"], a["D"], a["mean"], a["rstd"],
+                              a["M"], a["D"], a["dtype"], 1, a["img"], a["img_t"], a["img_p"], None)
+
+    def bwd(**bad):
+        a = dict(good, **bad)
+        assert bad, "a call without a fault would launch"
+        return lib.fs2_ln_bwd(a["dy"], a["D"], a["s"], a["D"], a["mean"], a["rstd"], a["gamma"],
+                              a["beta"], 0, 0.1, 3, None, 0, a["ds"], a["D"], None, 0.0, 0,
+                              a["dgamma"], a["dbeta"], a["dcol"], a["M"], a["D"], a["dtype"], 1,
+                              a["ws"], None)
+
+    for call in (fwd, bwd):
+        assert call(D=0) == -1 and call(D=1025) == -1         # 1 <= D <= 1024
+        assert call(dtype=7) == -1                            # fp32 and bf16 only
+        assert call(M=0) == 0 and call(M=-3) == 0             # an empty problem is a no-op
+        assert call(M=0, D=0, gamma=None, mean=None) == 0     # ... whatever else is passed
+        for name in ("gamma", "mean"):
+            assert call(**{name: None}) == -1, name
+    for name in ("x", "y"):
+        assert fwd(**{name: None}) == -1, name
+    assert bwd(ds=None) == -1
+    assert bwd(dgamma=p16, ws=p16) == -1                      # dgamma without dbeta
+    assert bwd(dbeta=p16, ws=p16) == -1
+    assert bwd(dgamma=p16, dbeta=p16) == -1                   # sums without a workspace
+    assert bwd(dcol=p16) == -1
+    # the padded image of y: bf16 only, whole utterances, pad below the length, 8-column chunks
+    assert fwd(img=p16, img_t=8, img_p=2, dtype=N.F32) == -1
+    assert fwd(img=p16, img_t=5, img_p=2) == -1               # M % img_t != 0
+    assert fwd(img=p16, img_t=8, img_p=8) == -1               # img_p >= img_t
+    assert fwd(img=p16, img_t=8, img_p=2, D=60) == -1         # D % 8 != 0
+
+    def slices(ws=p16, nslices=2, stride=64, n=64, out=p16):
+        return lib.fs2_sum_slices(ws, nslices, stride, n, out, 1, None)
+
+    assert slices(n=62) == -1 and slices(stride=66) == -1     # n, stride multiples of 4
+    assert slices(nslices=0) == -1
+    assert slices(ws=p16 + 4) == -1 and slices(out=p16 + 8) == -1   # 16-byte aligned pointers
+    assert slices(ws=None) == -1 and slices(out=None) == -1
+    assert slices(n=0) == 0
+
+
 def test_ctypes_argument_counts_match_header():
     """every prototype in include/fs2_hip.h has as many parameters as its ctypes signature in
     fastspeech2/_native.py (a parameter added on one side only shifts every later argument)"""
