@@ -55,7 +55,15 @@ struct AttnP {
   uint32_t seed, salt;
   uint32_t thr16;                // dropout threshold (fs2_thr16)
   int xflags;                    // FS2_ATTN_FLAGS (experiments build only: timing bits, WRONG results)
+  const int32_t* qbound;         // backward, optional [B]: dO rows >= qbound[b] are exact zeros
 };
+
+// end of the query rows of utterance b whose dO can be non-zero (backward; T without a bound).
+// Indexed by the utterance b, not by the tiled-mask index: the mask quirk changes which keys
+// are valid, not which dO rows are zero.
+__device__ __forceinline__ int attn_qend(const AttnP& p, int b) {
+  return p.qbound ? max(0, min(p.T, p.qbound[b])) : p.T;
+}
 
 __device__ __forceinline__ bf16x8 ld_frag(const bf16* g) { return *(const bf16x8*)g; }
 
@@ -579,6 +587,20 @@ __global__ void __launch_bounds__(W8 * 64 / QG, 1) attn_bwd_dq_kernel(AttnP p) {
   int blk, z;
   attn_block_coords(blk, z);
   const int b = z / p.H, h = z - b * p.H;
+  // A block whose queries all lie at or past the bound has dO = 0 in every row: D = 0 and
+  // dS = P * (0 - 0) = 0, so its dQ is exact zeros -- stored here, before any K / V traffic.
+  // It writes no D / row-hash workspace rows: the dK/dV kernel stops at the same bound, and
+  // every 64-query tile it still reads starts below the bound, hence inside a block (of 64 or
+  // 128 queries, a multiple of the tile) whose first query is below the bound too, which ran.
+  if (blk * (16 * W8) >= attn_qend(p, b)) {
+    for (int i = threadIdx.x; i < 16 * W8 * (DH / 8); i += NT) {
+      const int ql = i / (DH / 8), cc = i - ql * (DH / 8);
+      const int qr = blk * (16 * W8) + ql;
+      if (qr >= p.T) continue;
+      *(u32x4*)(p.dqkv + ((long)b * p.T + qr) * p.lddq + h * DH + cc * 8) = u32x4{0u, 0u, 0u, 0u};
+    }
+    return;
+  }
   const uint32_t dkey = fs2_drop_key(p.seed, p.salt);
   const bool drop = p.p_drop > 0.f;
   const bf16* Qb = p.qkv + (long)b * p.T * p.ldq + h * DH;
@@ -808,7 +830,9 @@ __global__ void __launch_bounds__(W8 * 64, 1) attn_bwd_dkv_kernel(AttnP p) {
   TileDma<DH, W8> dma;
   dma.init(wave, lane, 0);
   const i32x4 rsQ = make_rsrc(Qb), rsO = make_rsrc(dOb);
-  const int ntile_all = (p.T + 63) / 64;
+  // query tiles up to the bound only: a tile whose dO rows are all zero has dP = 0 and D = 0, so
+  // it adds P^T * 0 to dV and (P * 0)^T Q to dK -- exactly nothing
+  const int ntile_all = (attn_qend(p, b) + 63) / 64;
   // lse / D / row-hash rows of a tile: wave 0 streams them in by 4-byte LDS-DMA
   const long BHT = (long)p.B * p.H * p.T;
   const i32x4 rsL = make_rsrc(p.lse + (long)z * p.T), rsD = make_rsrc(p.dsum + (long)z * p.T);
@@ -1364,11 +1388,12 @@ extern "C" int fs2_attn_fwd(const void* qkv, int64_t ldq, const uint8_t* key_pad
   return 0;
 }
 
-extern "C" int fs2_attn_bwd(const void* qkv, int64_t ldq, const uint8_t* key_pad, int mask_mode,
-                            const void* out, int64_t ldo, const void* dout, int64_t lddo,
-                            const float* lse, int B, int H, int T, int dh, float scale,
-                            float p_drop, uint32_t seed, uint32_t salt, void* dqkv,
-                            int64_t lddq, float* workspace, int dtype, void* stream) {
+static int attn_bwd_impl(const void* qkv, int64_t ldq, const uint8_t* key_pad, int mask_mode,
+                         const void* out, int64_t ldo, const void* dout, int64_t lddo,
+                         const float* lse, int B, int H, int T, int dh, float scale,
+                         float p_drop, uint32_t seed, uint32_t salt, void* dqkv,
+                         int64_t lddq, float* workspace, const int32_t* q_bound, int dtype,
+                         void* stream) {
   if (int rc = check(B, H, T, dh, ldq, qkv, dtype)) return rc;
   if (!key_pad || !out || !dout || !lse || !dqkv || !workspace) return FS2_EINVAL;
   if (!a16(out) || !a16(dout) || !a16(dqkv) || (ldo % 8) || (lddo % 8) || (lddq % 8))
@@ -1378,7 +1403,7 @@ extern "C" int fs2_attn_bwd(const void* qkv, int64_t ldq, const uint8_t* key_pad
   p.o = (const bf16*)out; p.ldo = ldo;
   p.dout = (const bf16*)dout; p.lddo = lddo;
   p.dqkv = (bf16*)dqkv; p.lddq = lddq;
-  p.lse = (float*)lse; p.dsum = workspace;
+  p.lse = (float*)lse; p.dsum = workspace; p.qbound = q_bound;
   p.B = B; p.H = H; p.T = T; p.D = H * dh;
   p.scale = scale; p.scale_log2 = scale * LOG2E; p.p_drop = p_drop;
   p.inv_keep = p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f;
@@ -1394,6 +1419,31 @@ extern "C" int fs2_attn_bwd(const void* qkv, int64_t ldq, const uint8_t* key_pad
   }
   FS2_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int fs2_attn_bwd(const void* qkv, int64_t ldq, const uint8_t* key_pad, int mask_mode,
+                            const void* out, int64_t ldo, const void* dout, int64_t lddo,
+                            const float* lse, int B, int H, int T, int dh, float scale,
+                            float p_drop, uint32_t seed, uint32_t salt, void* dqkv,
+                            int64_t lddq, float* workspace, int dtype, void* stream) {
+  return attn_bwd_impl(qkv, ldq, key_pad, mask_mode, out, ldo, dout, lddo, lse, B, H, T, dh, scale,
+                       p_drop, seed, salt, dqkv, lddq, workspace, nullptr, dtype, stream);
+}
+
+// fs2_attn_bwd with a per-utterance query-row bound (device int32 [B]): the caller guarantees
+// that dO rows t >= q_bound[b] of utterance b are exact zeros, and the kernels skip the query
+// tiles past min(T, q_bound[b]) -- same bits as the unbounded call on such a dO.  The
+// workspace rows of skipped query blocks are left unwritten.  (The experiments build's paired
+// dK/dV kernel, FS2_ATTN_BWD=4, ignores the bound and walks every tile.)
+extern "C" int fs2_attn_bwd_bounded(const void* qkv, int64_t ldq, const uint8_t* key_pad,
+                                    int mask_mode, const void* out, int64_t ldo, const void* dout,
+                                    int64_t lddo, const float* lse, int B, int H, int T, int dh,
+                                    float scale, float p_drop, uint32_t seed, uint32_t salt,
+                                    void* dqkv, int64_t lddq, float* workspace,
+                                    const int32_t* q_bound, int dtype, void* stream) {
+  if (!q_bound) return FS2_EINVAL;
+  return attn_bwd_impl(qkv, ldq, key_pad, mask_mode, out, ldo, dout, lddo, lse, B, H, T, dh, scale,
+                       p_drop, seed, salt, dqkv, lddq, workspace, q_bound, dtype, stream);
 }
 
 // D = rowsum(dO * O) and the dropout row hashes of every query row (dQ kernel -> dK/dV kernel)

@@ -213,7 +213,32 @@ __device__ __forceinline__ int reflect_idx(int i, int T) {
   return i;
 }
 
-#define FS2_CHECK_LAUNCH()                         \
+// K-major weight gradient (conv_mode 6) over token-compacted images: K-tiles per split when only
+// the first k_eff of the K columns hold data (k_eff read on the device; the rest are zeros).
+// nk_host = the uncompacted count (K / 64 / nsplit).  At least 2 (the GEMM's prologue issues two
+// K-tiles), never more than nk_host: split s reads K-tiles [s * nk, (s + 1) * nk), all inside K.
+// Shared by the GEMM prologue and the transposes that zero-fill the columns it reads past k_eff.
+__device__ __forceinline__ int fs2_km_nk(int k_eff, int K, int nk_host, int nsplit) {
+  const int ke = min(max(k_eff, 0), K);
+  const int per = ((ke + 63) / 64 + nsplit - 1) / nsplit;
+  return min(nk_host, max(2, per));
+}
+
+// Columns utterance b keeps in the token-compacted images when its dY rows t >= e are exact zeros.
+// Uncompacted it holds the T + 2P columns from b * (T + 2P); the weight gradient needs the first
+// e + 2P of them (dY column P + t pairs with X columns t .. t + 2P).  Only whole 64-column
+// K-tiles of the uncompacted image that lie inside the rest are dropped, so every K-tile that
+// remains holds the same nonzero products at the same positions as an uncompacted tile, and a
+// dropped tile added exact zeros: per split the GEMM's fp32 sums are the uncompacted ones, bit
+// for bit.  (Dropping every column past e + 2P would shift the utterances against the K-tile
+// and MFMA boundaries and regroup the sums.)
+__device__ __forceinline__ int fs2_km_width(int b, int e, int T, int P) {
+  const int Tp = T + 2 * P;
+  const int lo = b * Tp + e + 2 * P, hi = (b + 1) * Tp;
+  return Tp - 64 * max(0, hi / 64 - (lo + 63) / 64);
+}
+
+#define FS2_CHECK_LAUNCH()                        \
   do {                                             \
     hipError_t e__ = hipGetLastError();            \
     if (e__ != hipSuccess) return (int)e__;        \

@@ -76,6 +76,7 @@ struct GemmP {
   int max_ctas;            // grid budget of the persistent kernels (blocks), 8..256
   int a_bytes, b_bytes;    // gemm_w4b_kernel: readable byte extents of A and B (zeros past them)
   int a_kw;                // gemm_w4b_kernel: tap-inner K order of an overlapping-row A (desc a_kw)
+  const int32_t* k_eff;    // conv_mode 6: device int, columns >= *k_eff of A and B are zeros (desc k_eff)
 };
 
 __device__ __forceinline__ u32x4 add_bf16x8(u32x4 a, u32x4 b) {
@@ -2415,7 +2416,15 @@ __global__ void __launch_bounds__(BNT, 1) gemm_ps_kernel(GemmP p) {
   const int nbx = (G - xcd + 7) >> 3;
   const int c0 = (int)((long)nunit * xcd / 8), c1 = (int)((long)nunit * (xcd + 1) / 8);
   const int mine = local < c1 - c0 ? (c1 - c0 - local + nbx - 1) / nbx : 0;
-  const int nk = nsplit > 1 ? p.k_per_split / 64 : (p.K + 63) / 64;
+  // BT with p.k_eff (token-compacted images, fs2_pad_transpose_bounded): only the first *k_eff
+  // of the K columns hold data, the rest are zeros, so every split walks fewer K-tiles.  Read
+  // once, here: nk, the unit's K base and the loop bounds below are fixed at entry as before
+  // (see the note on per-tile unit arithmetic above).  fs2_km_nk keeps nk >= 2 for the prologue
+  // and <= the host count, so split s still reads inside K, over columns the transposes zeroed.
+  const int nk_host = nsplit > 1 ? p.k_per_split / 64 : (p.K + 63) / 64;
+  const int nk = (BT && p.k_eff)
+                     ? __builtin_amdgcn_readfirstlane(fs2_km_nk(*p.k_eff, p.K, nk_host, nsplit))
+                     : nk_host;
   const int total = mine * nk;
   if (total == 0) return;
   // BT: this block's unit (split bt_sp, tile bt_tile), fixed for the whole launch
@@ -3188,6 +3197,8 @@ extern "C" int fs2_gemm(const fs2_gemm_desc* d, void* stream) {
   p.c_row_pad = p.c_row_t ? d->c_row_pad : 0;
   p.max_ctas = d->max_ctas > 0 && d->max_ctas < 256 ? max(8, d->max_ctas / 8 * 8) : 256;
   p.a_kw = d->a_kw > 0 ? d->a_kw : 0;
+  p.k_eff = d->k_eff;
+  if (p.k_eff && (d->conv_mode != 6 || p.K < 128)) return FS2_EINVAL;
   if (p.a_kw && (d->dtype != FS2_BF16 || !d->a_kmajor || !d->b_kmajor || d->conv_mode ||
                  batch > 1 || p.split_k > 1 || p.lda % 64 ||
                  (long)p.a_kw * p.lda != p.K))

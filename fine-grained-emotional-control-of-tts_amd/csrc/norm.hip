@@ -912,14 +912,67 @@ constexpr int PITCH = 144;          // LDS row pitch in bytes: 64 channels (128 
 // 8-token chunk jc), two passes of 32 rows, one 16-byte store each.
 // part (optional): the block's column sums of X over its 64 tokens (pads contribute zero /
 // their reflected copies: only the reflect = 0 image is summed), part[blockIdx.x][c]
+//
+// offs (optional): the token axis compacted.  offs = int32 [B + 1] column offsets on the device,
+// offs[0] = 0, offs[b + 1] = offs[b] + w_b, w_b = fs2_km_width(b, e_b, T, Pc) (Pc the conv's pad:
+// e_b + 2Pc <= w_b <= T + 2Pc, whole K-tiles dropped only), then >= 16 entries of INT32_MAX up to
+// a multiple of 16 (ops.km_offsets).  The caller knows dY is zero in the rows t >= e_b of
+// utterance b, so no product of the weight gradient needs them: utterance b occupies the
+// columns [offs[b], offs[b + 1]), its rows t < w_b - 2Pc.  The reflect image still reflects
+// about the true T (its columns reach t = w_b - Pc - 1); the zero image keeps P zero columns
+// on both sides.  With k_eff = offs[B], the GEMM reads K-tiles [0, ksplit * fs2_km_nk(..) * 64)
+// and its tap shifts reach P columns further: columns from k_eff to 64 past that end, and the
+// last 64 of the image, are written as zeros; the blocks between store nothing.  part arrives
+// zero-filled (pad_transpose_impl): only the blocks holding data write their partial, to the
+// row of their uncompacted K-tile.  That, and the alignment of the K-tiles, hold only for
+// offsets made by fs2_km_width.  The offsets are read with block-uniform indices only (scalar
+// loads, no LDS, no barrier): a per-block scan of the bounds in LDS cost more than the
+// compaction saved (54 vs 33 us for the decoder's dY image).
 __global__ void __launch_bounds__(256) pad_transpose_kernel(const bf16* X, long ldx, int B, int T,
                                                             int C, int P, int reflect, bf16* out,
-                                                            long ldo, int ncols, float* part) {
+                                                            long ldo, int ncols, float* part,
+                                                            const int32_t* __restrict__ offs,
+                                                            int ksplit) {
   __shared__ __attribute__((aligned(16))) char tile[TJ * PITCH];
   const int tid = threadIdx.x;
   const int j0 = blockIdx.x * TJ, c0 = blockIdx.y * TC;
   const int Tp = T + 2 * P;
-  const long jend = (long)B * Tp;
+  long jend = (long)B * Tp;
+  // compacted: the first utterance b0 of this block's columns, its start and the next four ends
+  int b0 = 0, s0 = 0, e4[4] = {0, 0, 0, 0};
+  int prow = blockIdx.x;   // row of this block's column-sum partial
+  if (offs) {
+    jend = min(max(offs[B], 0), ncols);
+    const int nk_host = ncols / 64 / ksplit;
+    const int kz = min(ncols, ksplit * fs2_km_nk((int)jend, ncols, nk_host, ksplit) * 64 + 64);
+    // nothing of such a block is read -- except the image's last 64 columns: a tap shift
+    // j - P < 0 at a row's first columns reads the end of the row before it, so those are
+    // always rewritten (zeros) and stale values never outlive a step there
+    if (j0 >= kz && j0 + TJ < ncols) return;
+    for (int c = 1; c <= B; c += 16) {   // b0 = #{b >= 1 : offs[b] <= j0}; the padding never counts
+      int v[16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) v[i] = offs[c + i];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) b0 += v[i] <= j0;
+    }
+    b0 = min(b0, B - 1);
+    s0 = offs[b0];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) e4[i] = offs[b0 + 1 + i];
+    // this block's K-tile in the uncompacted image (the last whole tiles of an utterance's
+    // columns count as the dropped ones, so a column within (b0 + 1) Tp mod 64 of the
+    // utterance's end sits behind them): its partial goes where the uncompacted block's went
+    // and the slice sum adds the same numbers in the same order; the partials of dropped
+    // tiles and of the blocks past the end stay the zeros they were filled with
+    if (j0 < jend) {
+      const int back = e4[0] - j0;
+      const int oj = back <= (((b0 + 1) * Tp) & 63) ? (b0 + 1) * Tp - back : b0 * Tp + (j0 - s0);
+      prow = oj >> 6;
+    } else {
+      prow = -1;
+    }
+  }
   {
     const int jr = tid >> 3, ch = tid & 7;
 #pragma unroll
@@ -927,11 +980,23 @@ __global__ void __launch_bounds__(256) pad_transpose_kernel(const bf16* X, long 
       const int jl = jr + 32 * pass, j = j0 + jl;
       u32x4 v = {0u, 0u, 0u, 0u};
       if (j < jend && c0 + ch * 8 < C) {
-        const int b = j / Tp;
-        int t = j - b * Tp - P;
+        int b, t, te = T;
+        if (offs) {   // the utterance whose column range holds j: offs[b] <= j < offs[b + 1]
+          b = b0;
+          int s = s0, e = e4[0];
+#pragma unroll
+          for (int i = 0; i < 3; ++i)
+            if (j >= e4[i]) { ++b; s = e4[i]; e = e4[i + 1]; }
+          while (j >= e && b + 1 < B) { ++b; s = e; e = offs[b + 1]; }   // > 4 utterances in 64 columns
+          t = j - s - P;
+          te = min(T, e - s - 2 * P);
+        } else {
+          b = j / Tp;
+          t = j - b * Tp - P;
+        }
         bool ok = true;
-        if (reflect) t = reflect_idx(t, T);
-        else ok = t >= 0 && t < T;
+        if (reflect) t = min(max(reflect_idx(t, T), 0), T - 1);
+        else ok = t >= 0 && t < te;
         if (ok) v = *(const u32x4*)(X + ((long)b * T + t) * ldx + c0 + ch * 8);
       }
       *(u32x4*)(tile + jl * PITCH + ch * 16) = v;
@@ -949,7 +1014,7 @@ __global__ void __launch_bounds__(256) pad_transpose_kernel(const bf16* X, long 
 #pragma unroll
       for (int e = 0; e < 4; ++e)
         w[e] = (unsigned)col[(2 * e) * (PITCH / 2)] | ((unsigned)col[(2 * e + 1) * (PITCH / 2)] << 16);
-      if (part) {   // 8 tokens per lane, then the 8 lanes of the row (fixed order)
+      if (part && prow >= 0) {   // 8 tokens per lane, then the 8 lanes of the row (fixed order)
         float s = 0.f;
 #pragma unroll
         for (int e = 0; e < 4; ++e)
@@ -957,12 +1022,48 @@ __global__ void __launch_bounds__(256) pad_transpose_kernel(const bf16* X, long 
         s += __shfl_xor(s, 1, 64);
         s += __shfl_xor(s, 2, 64);
         s += __shfl_xor(s, 4, 64);
-        if (jc == 0 && c < C) part[(long)blockIdx.x * C + c] = s;
+        if (jc == 0 && c < C) part[(long)prow * C + c] = s;
       }
       if (c >= C || j >= ncols) continue;
       *(u32x4*)(out + (long)c * ldo + j) = w;
     }
   }
+}
+
+__global__ void __launch_bounds__(256) zero_f32_kernel(float* x, long n) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) x[i] = 0.f;
+}
+
+// Row bounds of a padded batch's backward and the column offsets of its compacted K-major
+// images, from the lengths on the device: end[b] = clamp(len[b] + halo, 0, T), offs[0] = 0,
+// offs[b + 1] = offs[b] + fs2_km_width(b, end[b], T, P), offs[B + 1 .. noffs) = INT32_MAX.
+// One wave.
+__global__ void __launch_bounds__(64) grad_tail_bounds_kernel(const int64_t* len, int B, int T,
+                                                              int halo, int P, int32_t* end,
+                                                              int32_t* offs, int noffs) {
+  const int lane = threadIdx.x;
+  int carry = 0;
+  if (offs && lane == 0) offs[0] = 0;
+  for (int b0 = 0; b0 < B; b0 += 64) {
+    const int b = b0 + lane;
+    int w = 0;
+    if (b < B) {
+      const long v = (long)len[b] + halo;
+      const int e = (int)(v < 0 ? 0 : (v > T ? T : v));
+      w = fs2_km_width(b, e, T, P);
+      if (end) end[b] = e;
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int o = __shfl_up(w, d, 64);
+      if (lane >= d) w += o;
+    }
+    if (offs && b < B) offs[b + 1] = carry + w;
+    carry += __shfl(w, 63, 64);
+  }
+  if (offs)
+    for (int i = B + 1 + lane; i < noffs; i += 64) offs[i] = 0x7fffffff;
 }
 
 // token-major padded image (conv forward over the padded domain, fs2_pad_rows):
@@ -1191,24 +1292,65 @@ extern "C" int fs2_conv_fold(const float* Xpad, int nsplit, int64_t split_stride
 // this translation unit's dropout seed base (fs2_common.h)
 FS2_SEED_SETTER(fs2_seed_base_norm)
 
-extern "C" int fs2_pad_transpose(const void* X, int64_t ldx, int B, int T, int C, int P,
-                                 int reflect, void* out, int64_t ldo, int ncols, float* colsum,
-                                 float* workspace, int dtype, void* stream) {
+static int pad_transpose_impl(const void* X, int64_t ldx, int B, int T, int C, int P,
+                              int reflect, void* out, int64_t ldo, int ncols, float* colsum,
+                              float* workspace, const int32_t* offs, int ksplit, int dtype,
+                              void* stream) {
   if (B <= 0 || T <= 0 || C <= 0) return 0;
   if (dtype != FS2_BF16 || !X || !out || P < 0 || (reflect && P >= T)) return FS2_EINVAL;
   if ((C % 8) || (ldx % 8) || (ldo % 8) || (ncols % 8) || ncols < (long)B * (T + 2 * P) ||
       ldo < ncols || !a16(X) || !a16(out))
     return FS2_EALIGN;
   if (colsum && (reflect || !workspace)) return FS2_EINVAL;
+  if (offs && (ksplit < 1 || (ncols % (64 * ksplit)) || ncols < 128)) return FS2_EINVAL;
   dim3 grid((ncols + TJ - 1) / TJ, (C + TC - 1) / TC);
   hipStream_t s = (hipStream_t)stream;
+  if (offs && colsum) {   // the partial rows of dropped K-tiles have no writer
+    const long n = (long)grid.x * C;
+    hipLaunchKernelGGL(zero_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
+                       workspace, n);
+    FS2_CHECK_LAUNCH();
+  }
   hipLaunchKernelGGL(pad_transpose_kernel, grid, dim3(256), 0, s, (const bf16*)X, (long)ldx, B, T,
-                     C, P, reflect, (bf16*)out, (long)ldo, ncols, colsum ? workspace : nullptr);
+                     C, P, reflect, (bf16*)out, (long)ldo, ncols, colsum ? workspace : nullptr,
+                     offs, ksplit);
   FS2_CHECK_LAUNCH();
   if (colsum) {   // colsum[c] += sum over the token blocks' partials (fixed order)
     launch_reduce_parts(s, workspace, (int)grid.x, C, 1, colsum, nullptr, nullptr, 1);
     FS2_CHECK_LAUNCH();
   }
+  return 0;
+}
+
+extern "C" int fs2_pad_transpose(const void* X, int64_t ldx, int B, int T, int C, int P,
+                                 int reflect, void* out, int64_t ldo, int ncols, float* colsum,
+                                 float* workspace, int dtype, void* stream) {
+  return pad_transpose_impl(X, ldx, B, T, C, P, reflect, out, ldo, ncols, colsum, workspace,
+                            nullptr, 1, dtype, stream);
+}
+
+// fs2_pad_transpose with the token axis compacted (see pad_transpose_kernel): offs int32 on the
+// device, B + 1 column offsets followed by INT32_MAX padding (ops.km_offsets); ncols a multiple
+// of 64 * ksplit, where ksplit is the split_k of the conv_mode-6 GEMM that reads the image with
+// fs2_gemm_desc.k_eff = offs + B.
+extern "C" int fs2_pad_transpose_bounded(const void* X, int64_t ldx, int B, int T, int C, int P,
+                                         int reflect, void* out, int64_t ldo, int ncols,
+                                         float* colsum, float* workspace, const int32_t* offs,
+                                         int ksplit, int dtype, void* stream) {
+  if (!offs) return FS2_EINVAL;
+  return pad_transpose_impl(X, ldx, B, T, C, P, reflect, out, ldo, ncols, colsum, workspace, offs,
+                            ksplit, dtype, stream);
+}
+
+extern "C" int fs2_grad_tail_bounds(const int64_t* len, int B, int T, int halo, int P,
+                                    int32_t* end, int32_t* offs, int noffs, void* stream) {
+  if (B <= 0) return 0;
+  if (!len || T <= 0 || halo < 0 || P < 0 || (!end && !offs)) return FS2_EINVAL;
+  if (offs && (noffs < (B + 1 + 15) / 16 * 16 + 16 || (long)B * (T + 2L * P) >= 0x7fffffffL))
+    return FS2_EINVAL;
+  hipLaunchKernelGGL(grad_tail_bounds_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, len, B, T,
+                     halo, P, end, offs, noffs);
+  FS2_CHECK_LAUNCH();
   return 0;
 }
 

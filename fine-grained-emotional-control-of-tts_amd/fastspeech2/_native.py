@@ -64,7 +64,7 @@ class GemmDesc(ctypes.Structure):
         ("sB2", ctypes.c_int64), ("sC1", ctypes.c_int64), ("sC2", ctypes.c_int64),
         ("sR1", ctypes.c_int64), ("sR2", ctypes.c_int64), ("conv_dil", ctypes.c_int),
         ("c_row_t", ctypes.c_int), ("c_row_pad", ctypes.c_int), ("max_ctas", ctypes.c_int),
-        ("a_kw", ctypes.c_int),
+        ("a_kw", ctypes.c_int), ("k_eff", ctypes.c_void_p),
     ]
 
 
@@ -110,6 +110,8 @@ SIGNATURES = {
     "fs2_colsum_workspace_floats": (I64, [I, I]),
     "fs2_sum_slices": (I, [P, I, I64, I64, P, I, P]),
     "fs2_pad_transpose": (I, [P, I64, I, I, I, I, I, P, I64, I, P, P, I, P]),
+    "fs2_pad_transpose_bounded": (I, [P, I64, I, I, I, I, I, P, I64, I, P, P, P, I, I, P]),
+    "fs2_grad_tail_bounds": (I, [P, I, I, I, I, P, P, I, P]),
     "fs2_pad_rows": (I, [P, I64, I, I, I, I, I, I, P, I64, I, P]),
     "fs2_ln_fwd": (I, [P, I64, P, I64, Fl, U32, P, P, P, Fl, I, Fl, U32, P, P, I64, P, I64, P, P,
                        I, I, I, U32, P, I, I, P]),
@@ -120,6 +122,8 @@ SIGNATURES = {
     "fs2_attn_fwd": (I, [P, I64, P, I, I, I, I, I, Fl, Fl, U32, U32, P, I64, P, I, P]),
     "fs2_attn_bwd": (I, [P, I64, P, I, P, I64, P, I64, P, I, I, I, I, Fl, Fl, U32, U32, P, I64,
                          P, I, P]),
+    "fs2_attn_bwd_bounded": (I, [P, I64, P, I, P, I64, P, I64, P, I, I, I, I, Fl, Fl, U32, U32, P,
+                                 I64, P, P, I, P]),
     "fs2_attn_workspace_floats": (I64, [I, I, I]),
     "fs2_softmax_fwd": (I, [P, P, I, I, I, I, I, I, Fl, Fl, U32, U32, P, P, I, P]),
     "fs2_softmax_bwd": (I, [P, P, I, I, I, I, I, Fl, Fl, U32, U32, P, I, P]),

@@ -110,6 +110,10 @@ _AUX_ENERGY = N.exp_int("FS2_AUX_ENERGY", 1)
 # the pitch / energy embedding and speaker-embedding weight gradients on the side stream
 # (FS2_SIDE_SMALL=0: on the main stream, for A/B runs)
 _SIDE_SMALL = N.exp_int("FS2_SIDE_SMALL", 1)
+# decoder backward: skip the padded query rows whose gradients are exact zeros (engine
+# skip_grad_tail; experiments build, for A/B runs: FS2_GRAD_TAIL=0 turns it off, 1 bounds the
+# attention backward only, 3 (default) also compacts the K-major weight gradients)
+_GRAD_TAIL = N.exp_int("FS2_GRAD_TAIL", 3)
 
 
 def ps_plain_ok(M, lda, N, ldb, out_rows, ldc, out_bytes):
@@ -183,6 +187,7 @@ class FS2Engine:
         self.on_grads_ready = None   # optional callback(tag) for DP overlap
         self.timer = None            # optional KernelTimer: HIP events around tagged launches
         self._km = {}                # conv_mode-6 images, reused layer after layer (side stream)
+        self._offs = {}              # id(bound) -> (bound, P, column offsets), this backward's
         self._img = {}               # per-layer zero-padded dY images (_dy_image)
         self._fimg = {}              # padded FFN conv1 forward images (_fwd_image)
         # FusedTrainer.step sets adam_split = (optimizer, AdamW scalars): the backward then updates
@@ -196,6 +201,64 @@ class FS2Engine:
         self.dp_late = None
         self.n_adam_late = 0         # late AdamW launches from inside the backward (tests)
         self._adam_tabs = None
+        # Decoder backward over a padded batch: the gradient entering the decoder is exactly 0.0
+        # on every row t >= mel_len[b] (masked mel-linear output, masked PostNet data gradient),
+        # and the only backward op that moves gradient between query rows is a k > 1 conv's data
+        # gradient, by (k - 1) / 2 rows.  So in every decoder layer the gradient rows
+        # t >= mel_len[b] + _dec_halo() are exact zeros, and the fused attention backward gets
+        # that bound and skips them (same bits).  skip_grad_tail = False turns the skipping off;
+        # check_grad_tail (tests, with the skipping off) asserts the zero tail at every site
+        # that would receive the bound and lists the sites in grad_tail_checked.
+        self.skip_grad_tail = bool(_GRAD_TAIL)
+        self.check_grad_tail = False
+        self.grad_tail_checked = []
+
+    def _dec_halo(self):
+        """rows past mel_len[b] that the decoder stack's conv data gradients can reach: the sum
+        of (k - 1) / 2 over every FFN conv of every decoder layer (k = 9 and k = 1: 4 per layer)"""
+        return sum((self._wspecs[f"decoder.layers.{i}.pos_ffn.{j}.conv.weight"][2] - 1) // 2
+                   for i in range(self.cfg.dec_num_layers) for j in (0, 2))
+
+    def _postnet_halo(self):
+        """as _dec_halo for the PostNet: (k - 1) / 2 summed over its convs"""
+        return sum((kw - 1) // 2 for n, (_, _, kw) in self._wspecs.items()
+                   if n.startswith("postnet."))
+
+    def _tail_on(self):
+        return self.skip_grad_tail or self.check_grad_tail
+
+    def _km_offs(self, grad_end, P):
+        """column offsets of the compacted K-major images for this bound and conv pad (made with
+        the bound, _grad_end); None for another pad: that weight gradient stays uncompacted"""
+        ent = self._offs.get(id(grad_end))
+        if ent is None or ent[0] is not grad_end or ent[1] != P:
+            return None
+        return ent[2]
+
+    def _grad_end(self, mel_len, T, halo, P):
+        """int32 [B] on the device: min(T, mel_len[b] + halo), with the column offsets of the
+        K-major images compacted to it for conv pad P (kept for _km_offs until the next
+        backward).  One launch of our own and two torch.empty, like every other launch of the
+        step: no host sync, and nothing a stream capture treats differently (torch.cumsum and
+        friends inside a captured side-stream section made the capture fail)."""
+        end, offs = ops.grad_tail_bounds(mel_len.contiguous(), T, halo, P)
+        self._offs[id(end)] = (end, P, offs)
+        return end
+
+    def _tail_bound(self, site, dy, B, T, grad_end, L=None):
+        """the row bound a backward call site hands its kernel: ``grad_end`` with the skipping
+        on, else None.  Under check_grad_tail the rows t >= grad_end[b] of ``dy`` must be exact
+        zeros (host sync: tests only); dy holds L >= T rows per utterance, token t at row t."""
+        if grad_end is None:
+            return None
+        if self.check_grad_tail:
+            L = L or T
+            t = torch.arange(T, device=self.dev)[None, :] >= grad_end[:, None].long()
+            tail = dy[:B * L].reshape(B, L, -1)[:, :T][t]
+            nz = int((tail != 0).sum())
+            assert nz == 0, f"{site}: {nz} non-zero gradient elements past grad_end"
+            self.grad_tail_checked.append((site, int(tail.shape[0])))
+        return grad_end if self.skip_grad_tail else None
 
     def _fwd_image(self, rows, tail, C):
         """the FFN conv1 forward's padded image [rows + tail][C], one per shape: every layer's
@@ -645,17 +708,22 @@ class FS2Engine:
                       split_stride=Mp * C)
 
     def _wgrad(self, dY, lddy, X, ldx, M, T, wname, n_cols=None, gemm_tag=None, bias=None,
-               dy_img=None):
+               dy_img=None, grad_end=None):
         """weight gradient on the side stream; ``bias``: also the bias gradient (column sums of
         dY) -- fused into the K-major path's dY transpose, else an fs2_colsum pass; ``dy_img``:
-        dY lives in a zero-padded image (_dy_image), read from there"""
-        h = self._side_enter(dY, X, dy_img)
+        dY lives in a zero-padded image (_dy_image), read from there; ``grad_end``: int32 [B],
+        dY rows t >= grad_end[b] are exact zeros (the K-major path then skips them)"""
+        grad_end = self._tail_bound(wname, dY, M // T, T, grad_end,
+                                    T + self._wspecs[wname][2] - 1 if dy_img is not None else None)
+        if not _GRAD_TAIL & 2:
+            grad_end = None
+        h = self._side_enter(dY, X, dy_img, grad_end)
         tag = self._dtag("wgrad", wname, T)
         if tag:
             self._tic(tag)
         ctas = self._side_ctas if h is not None else 0
         done = self._wgrad_impl(dY, lddy, X, ldx, M, T, wname, n_cols, gemm_tag, bias, dy_img,
-                                ctas)
+                                ctas, grad_end)
         if tag:
             self._toc(tag)
         if bias is not None and not done:
@@ -696,12 +764,18 @@ class FS2Engine:
         return buf[64:64 + n]
 
     def _wgrad_km(self, dY, lddy, X, ldx, M, T, wname, gemm_tag=None, bias=None, dy_img=None,
-                  ctas=0):
+                  ctas=0, grad_end=None):
         """grad[O][KW][C] += sum_{b,t} dY[b,t,o] X[b, reflect(t+j-P), c] with both GEMM operands
         K-major: dY and X are first written channel-major over the padded token domain (T+2P
         columns per utterance; dY's pad columns zero, X's reflected), where tap j is a constant
         column shift j - P of X's image (fs2_pad_transpose + conv_mode 6).  Same sum as
-        _wgrad_impl's implicit-conv GEMM (SB Conv1d weight gradient, model.py:241-267)."""
+        _wgrad_impl's implicit-conv GEMM (SB Conv1d weight gradient, model.py:241-267).
+        ``grad_end`` (dY rows t >= grad_end[b] exact zeros): both images drop the whole K-tiles
+        past the bound (fs2_pad_transpose_bounded; whole tiles only, so the sums of a split do
+        not regroup and an S = 1 gradient is the uncompacted one bit for bit) and the GEMM takes its K from the
+        device: k_eff is the last of the column offsets (_km_offs), which are computed once per
+        bound and conv pad and shared by every layer -- neither the transposes nor the GEMM
+        prologue recompute a prefix sum.  Sizes, S and the slice sum are unchanged."""
         O, C, KW = self._wspecs[wname]
         P = (KW - 1) // 2
         B = M // T
@@ -716,34 +790,41 @@ class FS2Engine:
         XT = self._km_image("x", C, Kp)
         ws = self.ws(max(ops.pad_transpose_ws(Kp, O), 1))
         colsum = self.grads[bias] if bias is not None else None
+        keff, bk = None, {}
+        offs = self._km_offs(grad_end, P) if grad_end is not None and Kp >= 128 else None
+        if offs is not None:
+            keff, bk = offs[B:B + 1], dict(offs=offs, ksplit=S)
         if dy_img is not None:
             # the padded dY image already holds the zero pad rows: a plain transpose of its
-            # utterance rows (from image row P: T + 2P rows per utterance)
+            # utterance rows (from image row P: T + 2P rows per utterance; compacted: the first
+            # grad_end[b] + 2P of them)
             ops.pad_transpose(dy_img[P:], lddy, B, T + 2 * P, O, 0, 0, dYT, Kp, Kp,
-                              dt=self.dt, colsum=colsum, ws=ws)
+                              dt=self.dt, colsum=colsum, ws=ws, **bk)
         else:
             ops.pad_transpose(dY, lddy, B, T, O, P, 0, dYT, Kp, Kp, dt=self.dt, colsum=colsum,
-                              ws=ws)
-        ops.pad_transpose(X, ldx, B, T, C, P, 1, XT, Kp, Kp, dt=self.dt)
+                              ws=ws, **bk)
+        ops.pad_transpose(X, ldx, B, T, C, P, 1, XT, Kp, Kp, dt=self.dt, **bk)
         stride = O * ncol
         ws = self.ws(S * stride)
         if gemm_tag:
             self._tic(gemm_tag)
         ops.gemm(O, ncol, Kp, dYT, Kp, XT, Kp, ws, ncol, dt=self.dt, conv=(6, T, KW, C),
-                 c_fp32=1, split_k=S, split_stride=stride if S > 1 else 0, max_ctas=ctas)
+                 c_fp32=1, split_k=S, split_stride=stride if S > 1 else 0, max_ctas=ctas,
+                 k_eff=keff)
         if gemm_tag:
             self._toc(gemm_tag)
         ops.sum_slices(ws, S, stride, stride, self.grads[wname], accumulate=1)
         return True
 
     def _wgrad_impl(self, dY, lddy, X, ldx, M, T, wname, n_cols=None, gemm_tag=None, bias=None,
-                    dy_img=None, ctas=0):
+                    dy_img=None, ctas=0, grad_end=None):
         """grad[O][KW][C] += sum_m dY[m][o] * X[reflect(t+j-P)][c]   (fp32, accumulate).
         ``gemm_tag``: HIP events around the GEMM launch alone (bench.py's roofline entry for
         the FFN conv1 weight gradient), on the stream it runs on (the side stream)."""
         O, C, KW = self._wspecs[wname]
         if self._km_ok(O, C, KW, T, n_cols) and lddy % 8 == 0 and ldx % 8 == 0:
-            return self._wgrad_km(dY, lddy, X, ldx, M, T, wname, gemm_tag, bias, dy_img, ctas)
+            return self._wgrad_km(dY, lddy, X, ldx, M, T, wname, gemm_tag, bias, dy_img, ctas,
+                                  grad_end)
         if dy_img is not None:
             raise RuntimeError(f"{wname}: a padded dY image needs the K-major weight gradient")
         if n_cols is not None and n_cols != KW * C and KW == 1 and n_cols % 8 == 0 and self.dt == 1:
@@ -881,7 +962,9 @@ class FS2Engine:
                    ldt=ldt)
         return X2, ctx
 
-    def _fft_bwd(self, dX2, ctx, B, T, prefix, H, p_drop, seed):
+    def _fft_bwd(self, dX2, ctx, B, T, prefix, H, p_drop, seed, grad_end=None):
+        """``grad_end``: int32 [B], the layer's gradient rows t >= grad_end[b] are exact zeros
+        (the decoder over a padded batch, see __init__); None: no bound (the encoder)"""
         D = self.cfg.enc_d_model
         dh = D // H
         M = B * T
@@ -916,7 +999,7 @@ class FS2Engine:
         self._dgrad(dY, D, M, T, w2, dHc, F, gate=ctx["Hc"], ldg=F, **crow)
         self._wgrad(dHc, F, ctx["X1"], D, M, T, w1,
                     gemm_tag="ffn_conv1_wgrad." + prefix.split(".")[0],
-                    bias=prefix + "pos_ffn.0.conv.bias", dy_img=img)
+                    bias=prefix + "pos_ffn.0.conv.bias", dy_img=img, grad_end=grad_end)
         self._dgrad((img,) if pad else dHc, F, M, T, w1, dX1, D, residual=ds2, ldr=D)
         del dY, dHc, ds2, img
         lnws = self.ws(ops.ln_ws(M, D))
@@ -941,7 +1024,8 @@ class FS2Engine:
             args = (QKV, 3 * D, ctx["key_pad"], ctx["Att"], D, dAtt, D, ctx["lse"], B, H, T, dh,
                     1.0 / math.sqrt(dh), p_drop, seed, ctx["s_att"], dQKV, 3 * D)
             ws = self.ws(ops.attn_ws(B, H, T))
-            ops.attn_bwd(*args, dt=self.dt, ws=ws)
+            qb = self._tail_bound(prefix + "attn_bwd", dAtt, B, T, grad_end)
+            ops.attn_bwd(*args, dt=self.dt, ws=ws, q_bound=qb)
             if tag:
                 self._toc(tag)
             return self._qkv_bwd(dQKV, ctx, M, T, D, prefix, ds1)
@@ -1144,13 +1228,19 @@ class FS2Engine:
         ctx.update(convs=outs, q3=q3, p4=p4, ln3=(p4, mn3, rs3, s3))
         return post, ctx
 
-    def _postnet_bwd(self, d_post, d_mel_total, keep, ctx, B, T, p_drop, seed):
+    def _postnet_bwd(self, d_post, d_mel_total, keep, ctx, B, T, p_drop, seed, mel_len):
         """d_mel_total: grad already accumulated on mel (loss + residual); returns masked d_mel."""
         c = self.cfg
         E, NM = c.postnet_embedding_dim, c.n_mels
         M = B * T
         P, G = self.params, self.grads
         p4, mn3, rs3, s3 = ctx["ln3"]
+        # d_post is exactly 0.0 on the padded frames (masked loss) and each conv's data gradient
+        # spreads it (k - 1) / 2 rows: one bound for every PostNet weight gradient
+        pn_end = None
+        if self._tail_on():
+            pn_end = self._grad_end(mel_len, T, self._postnet_halo(),
+                                    (c.postnet_kernel_size - 1) // 2)
         dp4 = self.empty(M, NM)
         ops.ln_bwd(d_post, NM, p4, NM, mn3, rs3, P["postnet.ln3.weight"], P["postnet.ln3.bias"], dp4,
                    NM, M, NM, dt=self.dt, ws=self.ws(ops.ln_ws(M, NM)), seed=seed, p_o=p_drop,
@@ -1159,7 +1249,7 @@ class FS2Engine:
         wname = "postnet.conv_post.conv.weight"
         dq3 = self.empty(M, E)
         self._dgrad(dp4, NM, M, T, wname, dq3, E)
-        self._wgrad(dp4, NM, ctx["q3"], E, M, T, wname)
+        self._wgrad(dp4, NM, ctx["q3"], E, M, T, wname, grad_end=pn_end)
         x, mn, rs, s = ctx["ln2"]
         dx = self.empty(M, E)
         ops.ln_bwd(dq3, E, x, E, mn, rs, P["postnet.ln2.weight"], P["postnet.ln2.bias"], dx, E, M, E,
@@ -1182,12 +1272,12 @@ class FS2Engine:
                 dmel = self.empty(M, NM)
                 self._dgrad(dx, E, M, T, name + ".conv.weight", dmel, NM, residual=d_mel_total,
                             ldr=NM, row_scale_post=keep)
-                self._wgrad(dx, E, xin, ldx, M, T, name + ".conv.weight")
+                self._wgrad(dx, E, xin, ldx, M, T, name + ".conv.weight", grad_end=pn_end)
                 return dmel
             dprev = self.empty(M, E)
             self._dgrad(dx, E, M, T, name + ".conv.weight", dprev, E)
             self._wgrad(dx, E, xin, ldx, M, T, name + ".conv.weight",
-                        bias=name + ".conv.bias" if i != bias_done else None)
+                        bias=name + ".conv.bias" if i != bias_done else None, grad_end=pn_end)
             dx = dprev
 
     # ------------------------------------------------------------------ full forward
@@ -1353,6 +1443,7 @@ class FS2Engine:
                         and not self._adam_late_done and self._aux is not None
                         and self._side is not None and _ADAM_OVERLAP and self.dp_late[0]()):
                     self._adam_launch_late(self.dp_late[1])
+        self._offs = {}
         d_mel = d_mel.reshape(Mm, NM).to(self.adt).contiguous()
         d_post = d_post.reshape(Mm, NM).to(self.adt).contiguous()
         d_pitch = d_pitch.reshape(Mp).to(self.adt).contiguous()
@@ -1373,7 +1464,7 @@ class FS2Engine:
         d_mel_total = d_mel.clone()
         ops.add(d_mel_total, d_post, Mm * NM, 1.0, dt=self.dt)
         dmel = self._postnet_bwd(d_post, d_mel_total, keep_m, ctx["pn_ctx"], B, Tm, ctx["p_post"],
-                                 seed)
+                                 seed, ctx["mel_len"])
         notify("postnet")
         # mel linear (masked output, model.py:430)
         dXo = self.empty(Mm, D)
@@ -1385,9 +1476,16 @@ class FS2Engine:
                    P["decoder.norm.norm.bias"], dX, D, Mm, D, dt=self.dt, ws=self.ws(ops.ln_ws(Mm, D)),
                    dgamma=G["decoder.norm.norm.weight"], dbeta=G["decoder.norm.norm.bias"])
         notify("linear")
+        # one bound for the whole decoder stack (a layer nearer the output could take a smaller
+        # one).  The same bound holds for the decoder's token-major weight gradients, its data
+        # gradients and LayerNorm backwards, which still run over every row.
+        dec_end = None
+        if self._tail_on():
+            P1 = (self._wspecs["decoder.layers.0.pos_ffn.0.conv.weight"][2] - 1) // 2
+            dec_end = self._grad_end(ctx["mel_len"], Tm, self._dec_halo(), P1)
         for i in reversed(range(c.dec_num_layers)):
             dX = self._fft_bwd(dX, ctx["dec_ctx"][i], B, Tm, f"decoder.layers.{i}.", H_d,
-                               ctx["p_dec"], seed)
+                               ctx["p_dec"], seed, grad_end=dec_end)
             notify(f"decoder.layers.{i}")
         # LengthRegulator backward: segment sums (masked by the decoder input mask)
         dZ3 = self.empty(Mp, D)

@@ -71,8 +71,9 @@ def gemm(M, N_, K, A, lda, B, ldb, C, ldc, *, dt, a_kmajor=1, b_kmajor=1, conv=N
          c_conv_kw=0, bias=None, relu=0, gate=None, ldg=0, row_scale=None, residual=None, ldr=0,
          row_scale_post=None, accumulate=0, split_k=1, split_stride=0, kvalid=0, mvalid=0,
          nvalid=0, batch=1, batch_div=1, strides=None, conv_dil=1, c_row=None, max_ctas=0,
-         a_kw=0):
+         a_kw=0, k_eff=None):
     d = N.GemmDesc()
+    d.k_eff = _p(k_eff)       # conv_mode 6: device int32, effective K of token-compacted images
     d.conv_dil = conv_dil
     d.a_kw = a_kw             # tap-inner K order of an overlapping-row A (fs2_gemm_desc.a_kw)
     d.max_ctas = max_ctas     # persistent-kernel grid budget (0: one block per CU)
@@ -105,7 +106,59 @@ def conv_fold(Xpad, B, T, P, C, out, ldo, *, dt, residual=None, ldr=0, row_scale
                                _p(row_scale), _p(row_scale_post), dt, _s()), "fs2_conv_fold")
 
 
-def pad_transpose(X, ldx, B, T, C, P, reflect, out, ldo, ncols, *, dt, colsum=None, ws=None):
+def grad_tail_bounds(mel_len, T, halo, P):
+    """(end, offs) of a padded batch's backward from the int64 lengths on the device, one launch,
+    no host sync: end[b] = min(T, mel_len[b] + halo) int32 [B], offs as km_offsets(end, T, P)"""
+    B = mel_len.numel()
+    assert mel_len.dtype == torch.int64 and mel_len.is_contiguous()
+    end = torch.empty(B, dtype=torch.int32, device=mel_len.device)
+    offs = torch.empty(round_up(B + 1, 16) + 16, dtype=torch.int32, device=mel_len.device)
+    _chk(N.lib().fs2_grad_tail_bounds(_p(mel_len), B, T, halo, P, _p(end), _p(offs), offs.numel(),
+                                      _s()), "fs2_grad_tail_bounds")
+    return end, offs
+
+
+_TRI = {}   # (B, device) -> lower-triangular int32 ones, km_offsets' prefix-sum mask
+
+
+def km_offsets(grad_end, T, P):
+    """column offsets of the token-compacted conv_mode-6 images (fs2_pad_transpose_bounded):
+    int32, offs[0] = 0, offs[b + 1] = offs[b] + w_b, then INT32_MAX padding up to a multiple of
+    16 and 16 more.  w_b = T + 2P less the whole 64-column K-tiles of the uncompacted image that
+    lie in utterance b's columns from grad_end[b] + 2P on (fs2_km_width): the K-tiles that remain
+    are the uncompacted ones, so the GEMM's sums do not regroup.
+    ``grad_end``: int32 [B] on the device, 0 <= grad_end[b] <= T.
+    Device-side torch ops only (no host sync, capturable); offs[B:B + 1] is the GEMM's k_eff.
+    The prefix sum is a masked row sum, not torch.cumsum: the device scan behind cumsum queries
+    the device properties on the host, which a stream capture refuses."""
+    B = grad_end.numel()
+    key = (B, grad_end.device)
+    tri = _TRI.get(key)
+    if tri is None:
+        tri = torch.ones(B, B, dtype=torch.int32, device=grad_end.device).tril()
+        if not torch.cuda.is_current_stream_capturing():   # a graph's pool memory dies with it
+            _TRI[key] = tri
+    offs = torch.full((round_up(B + 1, 16) + 16,), 2 ** 31 - 1, dtype=torch.int32,
+                      device=grad_end.device)
+    offs[0] = 0
+    Tp = T + 2 * P
+    start = torch.arange(B, dtype=torch.int32, device=grad_end.device) * Tp
+    drop = ((start + Tp) // 64 - (start + grad_end + 2 * P + 63) // 64).clamp(min=0)
+    offs[1:B + 1] = (tri * (Tp - 64 * drop)[None, :]).sum(1, dtype=torch.int32)
+    return offs
+
+
+def pad_transpose(X, ldx, B, T, C, P, reflect, out, ldo, ncols, *, dt, colsum=None, ws=None,
+                  offs=None, ksplit=1):
+    """``offs`` (ops.km_offsets of the row bounds and the conv's pad): the token axis compacted
+    to the rows below each utterance's bound; ``ksplit``: the split_k of the conv_mode-6 GEMM
+    reading the image."""
+    if offs is not None:
+        assert offs.dtype == torch.int32 and offs.numel() >= round_up(B + 1, 16) + 16
+        _chk(N.lib().fs2_pad_transpose_bounded(_p(X), ldx, B, T, C, P, reflect, _p(out), ldo,
+                                               ncols, _p(colsum), _p(ws), _p(offs), ksplit, dt,
+                                               _s()), "fs2_pad_transpose_bounded")
+        return
     _chk(N.lib().fs2_pad_transpose(_p(X), ldx, B, T, C, P, reflect, _p(out), ldo, ncols,
                                    _p(colsum), _p(ws), dt, _s()), "fs2_pad_transpose")
 
@@ -170,7 +223,16 @@ def attn_fwd(qkv, ldq, key_pad, B, H, T, dh, scale, p_drop, seed, salt, out, ldo
 
 
 def attn_bwd(qkv, ldq, key_pad, out, ldo, dout, lddo, lse, B, H, T, dh, scale, p_drop, seed, salt,
-             dqkv, lddq, *, dt, ws, mask_mode=1):
+             dqkv, lddq, *, dt, ws, mask_mode=1, q_bound=None):
+    """``q_bound``: int32 [B] on the device; dO rows t >= q_bound[b] must be exact zeros, and
+    the query tiles past the bound are skipped (same bits as without it)."""
+    if q_bound is not None:
+        assert q_bound.dtype == torch.int32 and q_bound.numel() == B and q_bound.is_contiguous()
+        _chk(N.lib().fs2_attn_bwd_bounded(_p(qkv), ldq, _p(key_pad), mask_mode, _p(out), ldo,
+                                          _p(dout), lddo, _p(lse), B, H, T, dh, scale, p_drop,
+                                          seed & 0xffffffff, salt, _p(dqkv), lddq, _p(ws),
+                                          _p(q_bound), dt, _s()), "fs2_attn_bwd_bounded")
+        return
     _chk(N.lib().fs2_attn_bwd(_p(qkv), ldq, _p(key_pad), mask_mode, _p(out), ldo, _p(dout), lddo,
                               _p(lse), B, H, T, dh, scale, p_drop, seed & 0xffffffff, salt,
                               _p(dqkv), lddq, _p(ws), dt, _s()), "fs2_attn_bwd")

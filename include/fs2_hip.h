@@ -101,6 +101,11 @@ typedef struct fs2_gemm_desc {
    * bit 2; the forward's Wf: bit 3).  bf16, no split / batch / conv; always the 4-wave
    * kernel.                                                                                 */
   int a_kw;
+  /* conv_mode 6 only, optional: device int32 holding the effective K of token-compacted images
+   * (the last offset handed to fs2_pad_transpose_bounded): columns >= *k_eff of A and B are
+   * zeros up to where the transposes zero-filled, and every split walks max(2, ceil(ceil(k_eff / 64) / split_k))
+   * K-tiles instead of K / 64 / split_k.  Read on the device (no host sync).  NULL: off.      */
+  const int32_t* k_eff;
 } fs2_gemm_desc;
 
 int fs2_gemm(const fs2_gemm_desc* d, void* stream);
@@ -123,6 +128,32 @@ int fs2_conv_fold(const float* Xpad, int nsplit, int64_t split_stride, int B, in
 int fs2_pad_transpose(const void* X, int64_t ldx, int B, int T, int C, int P, int reflect,
                       void* out, int64_t ldo, int ncols, float* colsum, float* workspace,
                       int dtype, void* stream);
+/* fs2_pad_transpose with the token axis compacted, for a weight gradient whose dY rows
+ * t >= e_b of utterance b are exact zeros.  offs: device int32, B + 1 column offsets (offs[0] = 0,
+ * offs[b + 1] = offs[b] + w_b, Pc the conv's pad, 0 <= e_b <= T) followed by INT32_MAX up to a
+ * multiple of 16 and 16 more; read on the device.  w_b = T + 2 Pc - 64 r_b >= e_b + 2 Pc, r_b the
+ * whole 64-column K-tiles of the uncompacted image inside utterance b's columns from e_b + 2 Pc
+ * on: max(0, floor((b + 1)(T + 2 Pc) / 64) - ceil((b (T + 2 Pc) + e_b + 2 Pc) / 64)).  Only whole
+ * tiles are dropped, so the remaining ones hold what they held uncompacted and the GEMM's sums
+ * per split are unchanged bit for bit.  Utterance b keeps its rows t < w_b - 2 Pc and
+ * occupies the columns [offs[b], offs[b + 1]); the reflect image still reflects about T.  (A
+ * zero-padded token-major dY image, T + 2 Pc rows per utterance, is transposed with P = 0: its
+ * first w_b rows per utterance.)  Columns from the compacted end offs[B] to where a
+ * conv_mode-6 GEMM with split_k = ksplit and fs2_gemm_desc.k_eff = offs + B reads (64 past its
+ * last K-tile) and the last 64 columns are written as 0, the ones between are left untouched.
+ * ncols a multiple of 64 * ksplit, >= 128.  colsum as fs2_pad_transpose.                    */
+int fs2_pad_transpose_bounded(const void* X, int64_t ldx, int B, int T, int C, int P, int reflect,
+                              void* out, int64_t ldo, int ncols, float* colsum, float* workspace,
+                              const int32_t* offs, int ksplit, int dtype, void* stream);
+
+/* Row bounds of a padded batch's backward, from the utterance lengths on the device (no host
+ * sync): end[b] = clamp(len[b] + halo, 0, T) (int32 [B]; the gradient rows t >= end[b] are
+ * zeros, see fs2_attn_bwd_bounded) and the column offsets of the compacted conv_mode-6 images
+ * for a conv pad P (fs2_pad_transpose_bounded): offs[0] = 0, offs[b + 1] = offs[b] + w_b as
+ * defined there, offs[B + 1 .. noffs) = INT32_MAX, noffs >= round_up(B + 1, 16) + 16.  end or
+ * offs may be NULL.                                                                         */
+int fs2_grad_tail_bounds(const int64_t* len, int B, int T, int halo, int P, int32_t* end,
+                         int32_t* offs, int noffs, void* stream);
 
 /* out[i] (+)= sum_{s < nslices} ws[s*stride + i], i < n (fp32; n, stride multiples of 4,
  * 16-byte aligned): the sum of split-K weight-gradient slices written by fs2_gemm with
@@ -209,6 +240,15 @@ int fs2_attn_bwd(const void* qkv, int64_t ldq, const uint8_t* key_pad, int mask_
                  int64_t ldo, const void* dout, int64_t lddo, const float* lse, int B, int H,
                  int T, int dh, float scale, float p_drop, uint32_t seed, uint32_t salt,
                  void* dqkv, int64_t lddq, float* workspace, int dtype, void* stream);
+/* fs2_attn_bwd for a dO whose rows t >= q_bound[b] of utterance b are exact zeros (q_bound:
+ * device int32 [B], indexed by the utterance, read on the device): the query tiles past
+ * min(T, q_bound[b]) are skipped; bit-identical to fs2_attn_bwd on such a dO.  Workspace rows
+ * of skipped query blocks stay unwritten.                                                  */
+int fs2_attn_bwd_bounded(const void* qkv, int64_t ldq, const uint8_t* key_pad, int mask_mode,
+                         const void* out, int64_t ldo, const void* dout, int64_t lddo,
+                         const float* lse, int B, int H, int T, int dh, float scale,
+                         float p_drop, uint32_t seed, uint32_t salt, void* dqkv, int64_t lddq,
+                         float* workspace, const int32_t* q_bound, int dtype, void* stream);
 int64_t fs2_attn_workspace_floats(int B, int H, int T);
 
 /* ------------------------------------------------------------------------------------------
