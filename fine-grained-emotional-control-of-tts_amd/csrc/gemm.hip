@@ -2824,6 +2824,62 @@ __global__ void __launch_bounds__(BNT, 1) gemm_ps_kernel(GemmP p) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// ---- host side: validate (descriptor -> GemmArgs) -> plan_gemm (-> GemmPlan) -> launch ------
+// validate and plan_gemm make no HIP call; fs2_gemm_plan exposes them, so "which kernel does this
+// call take" is a host question (tests/golden/gemm_plans.json pins the answers).
+
+// Every GEMM instantiation of the library, one entry each.  `name` is the instantiation as the
+// profiler prints it (defaulted template arguments written out); gemm_kernel's, which the
+// profiler garbles, reads gemm_kernel<T, AK, BKM, GA, GB> with T spelled bf16 / float.
+// The rows stand in the order the kernels have always had in the code object: a moved row
+// moves every kernel behind it and with them the pc-relative offsets of their calls.
+struct GemmKernel { const char* name; void (*fn)(GemmP); int block; };
+#define FS2_K(block, ...) {#__VA_ARGS__, __VA_ARGS__, block}
+#define FS2_K128(T, GA, GB)   /* row 3 - (2 * ak + bk) */                                     \
+  FS2_K(NT, gemm_kernel<T, true, true, GA, GB>), FS2_K(NT, gemm_kernel<T, true, false, GA, GB>), \
+  FS2_K(NT, gemm_kernel<T, false, true, GA, GB>), FS2_K(NT, gemm_kernel<T, false, false, GA, GB>)
+#define FS2_KTILE(K, nt)      /* row tile_variant() */                                         \
+  FS2_K(nt, K<true, true, 0, 0>), FS2_K(nt, K<true, true, 1, 0>), FS2_K(nt, K<true, true, 4, 0>), \
+  FS2_K(nt, K<true, true, 5, 0>), FS2_K(nt, K<true, true, -1, -1>),                           \
+  FS2_K(nt, K<false, false, 0, 1>), FS2_K(nt, K<false, false, 0, 0>),                         \
+  FS2_K(nt, K<false, false, -1, -1>), FS2_K(nt, K<true, false, -1, -1>),                      \
+  FS2_K(nt, K<false, true, -1, -1>)
+const GemmKernel KERNELS[] = {
+    // K_W4B + 2 * (256-wide) + (bf16 output)
+    FS2_K(W4_NT, gemm_w4b_kernel<true, 6>), FS2_K(W4_NT, gemm_w4b_kernel<false, 6>),
+    FS2_K(W4_NT, gemm_w4b_kernel<true, 8>), FS2_K(W4_NT, gemm_w4b_kernel<false, 8>),
+    FS2_K(BNT, gemm_ps_kernel<0, 64, 0, 1>),   // K_PS6: conv_mode 6
+    FS2_K128(bf16, false, true),               // K_128: conv_mode 2
+    FS2_K128(bf16, true, true),                // K_128 + 4: every other bf16 call
+    // K_PS + {0: 192-wide with gate / residual; 1..3: 192-wide, 4..6: 256-wide, conv 0 / 1 / 4}
+    FS2_K(BNT, gemm_ps_kernel<0, 48, 1, 0>),
+    FS2_K(BNT, gemm_ps_kernel<0, 48, 0, 0>), FS2_K(BNT, gemm_ps_kernel<1, 48, 0, 0>),
+    FS2_K(BNT, gemm_ps_kernel<4, 48, 0, 0>),
+    FS2_K(BNT, gemm_ps_kernel<0, 64, 0, 0>), FS2_K(BNT, gemm_ps_kernel<1, 64, 0, 0>),
+    FS2_K(BNT, gemm_ps_kernel<4, 64, 0, 0>),
+    // K_PK + {0: 256 x 128, 1: 128 x 128, 2: 128 x 64}
+    FS2_K(BNT, gemm_pk_kernel<4, 4>), FS2_K(BNT, gemm_pk_kernel<2, 4>), FS2_K(BNT, gemm_pk_kernel<2, 2>),
+    // K_256R + {0, 1: register-direct epilogue, conv 0 / 1; 2..5: conv 0 / 1 / 4 / 5}
+    FS2_K(G4_NT, gemm256r_kernel<0, true, 64>), FS2_K(G4_NT, gemm256r_kernel<1, true, 64>),
+    FS2_K(G4_NT, gemm256r_kernel<0, false, 64>), FS2_K(G4_NT, gemm256r_kernel<1, false, 64>),
+    FS2_K(G4_NT, gemm256r_kernel<4, false, 64>), FS2_K(G4_NT, gemm256r_kernel<5, false, 64>),
+    FS2_KTILE(gemm256_kernel, G4_NT),          // K_256
+    FS2_KTILE(gemm_big_kernel, BNT),           // K_BIG
+    FS2_K128(float, false, false),             // K_F32
+};
+enum { K_W4B = 0, K_PS6 = 4, K_128 = 5, K_PS = 13, K_PK = 20, K_256R = 23, K_256 = 29, K_BIG = 39,
+       K_F32 = 49, K_COUNT = 53 };
+static_assert(sizeof(KERNELS) / sizeof(KERNELS[0]) == K_COUNT, "kernel table out of step");
+
+// what validate makes of a descriptor: the parameter block (128 x 128 tiling, caller's split)
+// and the host-only values no kernel sees
+struct GemmArgs { GemmP p; int dtype, ak, bk, batch; };
+
+// plan_gemm's answer: a row of KERNELS, the grid, and the parameter block as that kernel
+// receives it (tiles_m, tiles_n, split_k, k_per_split, vec_ok, accumulate, a_bytes, b_bytes and
+// g4_flags rewritten)
+struct GemmPlan { int kernel; dim3 grid; GemmP p; };
+
 // compile-time A-operand conv variant for the large-tile kernels: 0 plain, 1 / 4 conv with
 // taps aligned to the k-granule, -1 anything else (run-time generic path)
 int conv_variant(const GemmP& q, int granule) {
@@ -2833,343 +2889,24 @@ int conv_variant(const GemmP& q, int granule) {
   return -1;
 }
 
-template <typename T, bool GA, bool GB>
-void launch4(const GemmP& p, dim3 grid, hipStream_t s, int ak, int bk) {
-  if (ak && bk) hipLaunchKernelGGL((gemm_kernel<T, true, true, GA, GB>), grid, dim3(NT), 0, s, p);
-  else if (ak && !bk) hipLaunchKernelGGL((gemm_kernel<T, true, false, GA, GB>), grid, dim3(NT), 0, s, p);
-  else if (!ak && bk) hipLaunchKernelGGL((gemm_kernel<T, false, true, GA, GB>), grid, dim3(NT), 0, s, p);
-  else hipLaunchKernelGGL((gemm_kernel<T, false, false, GA, GB>), grid, dim3(NT), 0, s, p);
-}
-
-template <typename T>
-int launch_gemm(const GemmP& p, int gz, hipStream_t s, int ak, int bk) {
-  dim3 grid(p.tiles_m * p.tiles_n, 1, gz);
-  if constexpr (sizeof(T) == 2) {
-    // bf16: LDS-DMA for both operands, except the reflect-fold dgrad operand (register staged)
-    static const bool no_big = getenv_flag("FS2_GEMM_NO_BIG");
-    const int tiles_big = ((p.M + BBM - 1) / BBM) * p.tiles_n;
-    const int batch = p.split_k > 1 ? 1 : gz;
-    // weight-gradient GEMMs (fp32 accumulate, no epilogue ops): the big kernel picks its own
-    // K split; split > 1 takes the LDS-staged atomic epilogue (row-contiguous atomics)
-    const bool wgrad = p.split_stride == 0 && p.c_fp32 && (p.accumulate || p.split_k > 1) &&
-                       batch == 1 && !p.gate &&
-                       !p.residual && !p.bias && !p.row_scale && !p.row_scale_post && !p.relu &&
-                       p.c_conv_kw == 0 && p.vec_align;
-    int split_big = 1;
-    if (wgrad) {
-      const int nk = (p.K + 63) / 64;
-      // ~one round of blocks: fewer K slices halve the fp32 atomics (decoder QKV weight
-      // gradient 95 -> 75 us vs two rounds); FS2_WGRAD_BIG_TARGET overrides for A/B runs
-      static const int tgt = getenv_int("FS2_WGRAD_BIG_TARGET", 240);
-      split_big = max(1, min((tgt + tiles_big - 1) / tiles_big, nk / 8));
-    }
-    const bool slices = p.split_stride > 0 && p.split_k > 1;  // caller-chosen split, plain stores
-    // persistent 256x128 kernel: short-K plain GEMMs (FS2_GEMM_NO_PK=1 restores the per-tile
-    // kernels for A/B runs); 32-bit buffer offsets must cover A, B, C and the gate/residual
-    static const bool no_pk = getenv_flag("FS2_GEMM_NO_PK");
-    const long lim = 0x7fffffffL;
-    const long crows = p.c_row_t && p.c_row_pad > 0
-                           ? p.mvalid + ((long)p.mvalid / p.c_row_t + 1) * p.c_row_pad
-                           : p.mvalid;
-    const bool pk_fits = (long)p.M * p.lda * 2 < lim && (long)p.N * p.ldb * 2 < lim &&
-                         crows * p.ldc * (p.c_fp32 ? 4 : 2) < lim &&
-                         (long)p.mvalid * (p.gate ? p.ldg : p.ldr) * 2 < lim;
-    // the large-tile kernels address their operands through 32-bit buffer offsets (per batch
-    // entry); operands beyond 2 GiB take the pointer-based 128x128 kernel instead
-    const long a_rows = ak ? (long)(p.conv_mode ? p.M + 2L * p.conv_p : p.M) : (long)min(p.K, p.kvalid);
-    const long b_rows = bk ? (long)p.N : (long)min(p.K, p.kvalid);
-    const bool big_fits = a_rows * p.lda * 2 < lim && b_rows * p.ldb * 2 < lim;
-    // persistent 256 x 256 / 256 x 192 kernel: long-K K-major GEMMs without gate / residual
-    // operands (FS2_GEMM_NO_PS=1 restores the per-tile kernels for A/B runs)
-    static const bool no_ps = getenv_flag("FS2_GEMM_NO_PS");
-    // the 4-wave 128 x 128-per-wave kernel: plain K-major GEMMs with wide outputs and long K
-    // (FS2_GEMM_W4=0 in the experiments build: the 8-wave kernels, for A/B runs)
-    static const bool w4_on = getenv_int("FS2_GEMM_W4", 1) != 0;
-    // K >= 2048 and >= 160 tiles: the decoder conv2 forward (K = 1536) measured 52 vs 49 us on
-    // the short-K persistent kernel, the encoder's (50 tiles of 256 x 192) 43 us
-    static const int w4_min_k = getenv_int("FS2_W4_MIN_K", 2048);
-    static const int w4_min_tiles = getenv_int("FS2_W4_MIN_TILES", 160);
-    {
-      const long a_ext = ak ? (long)(p.M - 1) * p.lda + p.K : 0;
-      const long b_ext = bk ? (long)(p.N - 1) * p.ldb + p.K : 0;
-      const bool w4 = w4_on && ak && bk && p.conv_mode == 0 && batch == 1 && p.split_k <= 1 &&
-                      !p.accumulate && !p.gate && !p.residual && !p.row_scale && !p.row_scale_post &&
-                      p.K % 128 == 0 && p.K >= (p.a_kw ? 256 : max(256, w4_min_k)) &&
-                      (p.a_kw || (p.N >= 384 && p.M >= 2048)) &&
-                      p.nvalid % 4 == 0 && p.ldc % 4 == 0 && p.vec_align &&
-                      a_ext * 2 < 0x7fffffffL && b_ext * 2 < 0x7fffffffL &&
-                      ((long)p.M + 257) * p.lda * 2 < 0x7fffffffL &&
-                      ((long)p.N + 257) * p.ldb * 2 < 0x7fffffffL;
-      // tile width by rounds x width over the 256 CUs (ties to the wider tile)
-      const int tm4 = (p.M + 255) / 256;
-      const int t256 = tm4 * ((p.N + 255) / 256), t192 = tm4 * ((p.N + 191) / 192);
-      const bool w192 = (long)((t192 + 255) / 256) * 192 < (long)((t256 + 255) / 256) * 256;
-      if (p.a_kw && !w4) return FS2_EINVAL;   // the tap-inner order exists on this kernel only
-      if (w4 && ((w192 ? t192 : t256) >= w4_min_tiles || p.a_kw)) {
-        GemmP q = p;
-        q.tiles_m = tm4;
-        q.tiles_n = w192 ? (p.N + 191) / 192 : (p.N + 255) / 256;
-        q.a_bytes = (int)(a_ext * 2);
-        q.b_bytes = (int)(b_ext * 2);
-        q.g4_flags = getenv_int("FS2_W4_FLAGS", 0);
-        const dim3 g(q.tiles_m * q.tiles_n);
-        if (w192) {
-          if (p.c_fp32) hipLaunchKernelGGL((gemm_w4b_kernel<true, 6>), g, dim3(W4_NT), 0, s, q);
-          else hipLaunchKernelGGL((gemm_w4b_kernel<false, 6>), g, dim3(W4_NT), 0, s, q);
-        } else {
-          if (p.c_fp32) hipLaunchKernelGGL((gemm_w4b_kernel<true, 8>), g, dim3(W4_NT), 0, s, q);
-          else hipLaunchKernelGGL((gemm_w4b_kernel<false, 8>), g, dim3(W4_NT), 0, s, q);
-        }
-        FS2_CHECK_LAUNCH();
-        return 0;
-      }
-    }
-    if (p.conv_mode == 6) {
-      if (!p.vec_align) return FS2_EALIGN;
-      GemmP q = p;
-      q.g4_flags = getenv_int("FS2_PS_FLAGS", 0);
-      q.tiles_m = (p.M + 255) / 256;
-      q.tiles_n = (p.N + 255) / 256;
-      const int nu = q.tiles_m * q.tiles_n * max(1, p.split_k);
-      if (nu > 1024) return FS2_EINVAL;   // one unit per block (gemm_ps_kernel BT)
-      const int g = (nu + 7) / 8 * 8;
-      hipLaunchKernelGGL((gemm_ps_kernel<0, 64, 0, 1>), dim3(g), dim3(BNT), 0, s, q);
-      FS2_CHECK_LAUNCH();
-      return 0;
-    }
-    // FS2_PS_MODES: bit 0 plain, bit 1 reflect conv (fwd), bit 2 padded-domain conv (dgrad).
-    // Default 5: in the bench step the unsplit decoder conv1 data gradient gains 0.15-0.2 ms,
-    // while the conv1 forward measured 0-0.1 ms slower than gemm256_kernel (A/B runs).
-    // Short K (256 <= K < 2048) when the tiles fill at least 200 of the 256 CUs: the decoder's
-    // N = 384 / 1152 projections and FFN conv2 forward (M = 31264; tools/pk_bench.py: conv2 fwd
-    // 63.8 -> 49.1 us, out_proj 29.1 -> 22.0, in_proj 65.6 -> 52.6); the encoder's 25-row-tile
-    // shapes stay on the per-tile kernels (ps 30 -> 43 us).  FS2_PS_MIN_K / FS2_PS_SHORT_TILES
-    // override for A/B runs.
-    static const int ps_modes = getenv_int("FS2_PS_MODES", 5);
-    static const int ps_min_k = getenv_int("FS2_PS_MIN_K", 256);
-    static const int ps_short_tiles = getenv_int("FS2_PS_SHORT_TILES", 200);
-    const int cm_ps = p.conv_mode == 0 ? 0
-                      : ((p.conv_mode == 1 || p.conv_mode == 4) && p.conv_dil == 1 && p.conv_c % 64 == 0
-                             ? p.conv_mode : -1);
-    const bool ps_on = cm_ps >= 0 && (ps_modes >> (cm_ps == 0 ? 0 : (cm_ps == 1 ? 1 : 2))) & 1;
-    // tile width by rounds x width over the 256 CUs (ties to the wider tile)
-    const int ps_tm = (p.M + 255) / 256;
-    const int ps_t256 = ps_tm * ((p.N + 255) / 256), ps_t192 = ps_tm * ((p.N + 191) / 192);
-    // a gate / residual operand (plain A only) takes the 256 x 192 instance (its register budget)
-    const bool ps_op = p.gate || p.residual;
-    // a gate / residual operand takes the 256 x 192 instance (a 256 x 128 one, free of the
-    // spills of this one, measured slower: decoder gated dgrad 105-110 -> 120-122 us, step
-    // 18.05-18.11 -> 18.23-18.25 ms, tools/r04_eo.sh)
-    const bool ps_w192 = ps_op ||
-                         (long)((ps_t192 + 255) / 256) * 192 < (long)((ps_t256 + 255) / 256) * 256;
-    const int ps_nt = ps_w192 ? ps_t192 : ps_t256;
-    // a padded-domain output (c_row_t) exists only on this kernel: it takes every such GEMM
-    const bool ps_k = p.K >= 2048 || (p.K >= max(ps_min_k, 128) && ps_nt >= ps_short_tiles) ||
-                      (p.c_row_t && p.K >= 128);
-    const bool ps_go = !no_ps && ak && bk && ps_on && batch == 1 && p.split_k <= 1 && p.vec_ok &&
-        !p.accumulate && !(p.gate && p.residual) && (!ps_op || cm_ps == 0) && p.relu <= 1 && ps_k &&
-        p.N >= 128 && pk_fits;
-    if (p.c_row_t && !ps_go) return FS2_EINVAL;
-    if (!ps_go && !big_fits && p.conv_mode != 6) {
-      if (p.conv_mode == 2) launch4<T, false, true>(p, grid, s, ak, bk);
-      else launch4<T, true, true>(p, grid, s, ak, bk);
-      FS2_CHECK_LAUNCH();
-      return 0;
-    }
-    if (ps_go) {
-      GemmP q = p;
-      q.g4_flags = getenv_int("FS2_PS_FLAGS", 0);
-      q.tiles_m = ps_tm;
-      const bool w192 = ps_w192;
-      q.tiles_n = w192 ? (p.N + 191) / 192 : (p.N + 255) / 256;
-      const int nt = q.tiles_m * q.tiles_n;
-      const int cus = p.max_ctas;
-      const int g = nt < cus ? (nt + 7) / 8 * 8 : cus;
-      if (w192) {
-        if (ps_op) hipLaunchKernelGGL((gemm_ps_kernel<0, 48, 1>), dim3(g), dim3(BNT), 0, s, q);
-        else if (cm_ps == 0) hipLaunchKernelGGL((gemm_ps_kernel<0, 48>), dim3(g), dim3(BNT), 0, s, q);
-        else if (cm_ps == 1) hipLaunchKernelGGL((gemm_ps_kernel<1, 48>), dim3(g), dim3(BNT), 0, s, q);
-        else hipLaunchKernelGGL((gemm_ps_kernel<4, 48>), dim3(g), dim3(BNT), 0, s, q);
-      } else {
-        if (cm_ps == 0) hipLaunchKernelGGL((gemm_ps_kernel<0, 64>), dim3(g), dim3(BNT), 0, s, q);
-        else if (cm_ps == 1) hipLaunchKernelGGL((gemm_ps_kernel<1, 64>), dim3(g), dim3(BNT), 0, s, q);
-        else hipLaunchKernelGGL((gemm_ps_kernel<4, 64>), dim3(g), dim3(BNT), 0, s, q);
-      }
-      FS2_CHECK_LAUNCH();
-      return 0;
-    }
-    // narrow outputs with K >= 1152 (FFN conv2 forward, QKV data gradient) measured faster
-    // on the per-tile 256x128 kernel: decoder 70.5 -> 63.6 and 58.3 -> 55.6 us, encoder
-    // 33.7 -> 29.5 and 32.7 -> 29.0 (tools/gemm_bench.py, FS2_GEMM_NO_PK A/B);
-    // FS2_PK_NARROW=1 keeps them on the persistent kernel
-    static const bool pk_narrow = getenv_flag("FS2_PK_NARROW");
-    const bool pk_shape = p.K <= 768 || p.N > 512 || pk_narrow;
-    const bool pk_ok = !no_pk && ak && bk && p.conv_mode == 0 && batch == 1 && p.split_k <= 1 &&
-                       p.vec_ok && !p.accumulate && !(p.gate && p.residual) && p.K > 64 && pk_fits;
-    // tile of the persistent short-K kernel: 256 x 128 where those tiles fill most of a round
-    // (the decoder's shapes that gemm_ps_kernel does not take); below 160 such tiles (the
-    // encoder / predictor shapes, M = 6400) 128 x 128 or 128 x 64 tiles, whichever finishes in
-    // fewer per-CU tile-areas (two 128 x 64 blocks share a CU) -- K up to 4096 there, since the
-    // per-tile 256 x 128 kernel that takes the narrow long-K shapes fills 75 of the 256 CUs.
-    // FS2_PK_CFG = 44 / 24 / 22 forces one for A/B runs.
-    int pk_cfg = 0;
-    if (pk_ok) {
-      const long t44 = (long)((p.M + 255) / 256) * ((p.N + 127) / 128);
-      const long t24 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
-      const long t22 = (long)((p.M + 127) / 128) * ((p.N + 63) / 64);
-      // per-CU work in 128 x 128 tile units over the rounds each needs (ties: larger tile)
-      const long c44 = (t44 + 255) / 256 * 2, c24 = (t24 + 255) / 256, c22 = (t22 + 511) / 512;
-      long best = 1L << 40;
-      if (p.K <= 1536 && pk_shape) { pk_cfg = 44; best = c44; }
-      if (t44 < 400 && p.K <= 4096) {
-        if (c24 < best) { pk_cfg = 24; best = c24; }
-        if (c22 < best) { pk_cfg = 22; best = c22; }
-      }
-      static const int force = getenv_int("FS2_PK_CFG", 0);
-      if (force == 44 || force == 24 || force == 22) pk_cfg = force;
-    }
-    if (pk_cfg) {
-      GemmP q = p;
-      q.g4_flags = getenv_int("FS2_PK_FLAGS", 0);
-      const int TM = pk_cfg == 44 ? 256 : 128, TN = pk_cfg == 22 ? 64 : 128;
-      q.tiles_m = (p.M + TM - 1) / TM;
-      q.tiles_n = (p.N + TN - 1) / TN;
-      const int nt = q.tiles_m * q.tiles_n;
-      const int slots = (pk_cfg == 22 ? 2 : 1) * p.max_ctas;   // blocks resident at once (LDS)
-      // >= 8 blocks: every XCD chunk needs a block (blocks with no tile exit at once)
-      const int g = nt < slots ? (nt + 7) / 8 * 8 : slots;
-      if (pk_cfg == 44) hipLaunchKernelGGL((gemm_pk_kernel<4, 4>), dim3(g), dim3(BNT), 0, s, q);
-      else if (pk_cfg == 24) hipLaunchKernelGGL((gemm_pk_kernel<2, 4>), dim3(g), dim3(BNT), 0, s, q);
-      else hipLaunchKernelGGL((gemm_pk_kernel<2, 2>), dim3(g), dim3(BNT), 0, s, q);
-      FS2_CHECK_LAUNCH();
-      return 0;
-    }
-    // 256x256 phased kernel: wide outputs (< 10 % column padding; the QKV projection's
-    // N = 1152 pads 11 % and measured 100 vs 85 us on the 256x128 kernel at M = 31264)
-    static const bool no256 = getenv_flag("FS2_GEMM_NO256");
-    const int tm256 = (p.M + 255) / 256, tn256 = (p.N + 255) / 256;
-    const int tiles256 = tm256 * tn256;
-    const bool wide = p.N >= 512 && tn256 * 256 * 100 <= p.N * 110;
-    int split256 = 1;
-    if (wgrad) {
-      const int nk = (p.K + 63) / 64;
-      split256 = max(1, min((240 + tiles256 - 1) / tiles256, nk / 8));
-    }
-    // from 150 tiles: the encoder FFN conv1 forward (M = 6400, N = 1536: 150 tiles of 256^2 in
-    // one round vs 300 of 256x128 in 1.2 rounds) 122 -> 112 us; FS2_G4_MIN_TILES overrides
-    static const int g4_min = getenv_int("FS2_G4_MIN_TILES", 150);
-    const bool use256 = !no256 && wide && p.conv_mode != 2 &&
-                        ((p.vec_ok && p.split_k <= 1 && tiles256 * batch >= g4_min) ||
-                         (slices && p.vec_ok && tiles256 * p.split_k >= 160) ||
-                         (wgrad && tiles256 * split256 >= 160));
-    if (use256) {
-      GemmP q = p;
-      q.g4_flags = getenv_int("FS2_G4_FLAGS", 0);
-      q.tiles_m = tm256;
-      q.tiles_n = tn256;
-      int gz2 = slices ? p.split_k : gz;
-      if (wgrad) {
-        q.k_per_split = ((p.K + split256 - 1) / split256 + 63) / 64 * 64;
-        q.split_k = (p.K + q.k_per_split - 1) / q.k_per_split;
-        q.vec_ok = q.split_k == 1;
-        q.accumulate = 1;
-        gz2 = q.split_k;
-      }
-      dim3 g2(tiles256, 1, gz2);
-      const int cm = conv_variant(q, 32);
-      // full-row regions (gemm256r_kernel) for K-major A and B with 64-aligned taps;
-      // FS2_G4R=0 (experiments build) keeps gemm256_kernel
-      static const bool g4r = getenv_int("FS2_G4R", 1) != 0;
-      const int cm64 = conv_variant(q, 64);
-      if (ak && bk && g4r && cm64 >= 0) {
-        // register-direct epilogue (TR): bf16 output, no gate, one K split, 8-column granules
-        static const bool g4tr = getenv_int("FS2_G4R_TR", 1) != 0;
-        const bool tr = g4tr && q.vec_ok && !q.c_fp32 && !q.gate && q.split_k <= 1 &&
-                        q.nvalid % 8 == 0 && q.ldc % 8 == 0 && (!q.residual || q.ldr % 8 == 0) &&
-                        (q.relu <= 1) && !q.accumulate;
-        if (cm64 == 0 && tr) hipLaunchKernelGGL((gemm256r_kernel<0, true>), g2, dim3(G4_NT), 0, s, q);
-        else if (cm64 == 1 && tr) hipLaunchKernelGGL((gemm256r_kernel<1, true>), g2, dim3(G4_NT), 0, s, q);
-        else if (cm64 == 0) hipLaunchKernelGGL((gemm256r_kernel<0>), g2, dim3(G4_NT), 0, s, q);
-        else if (cm64 == 1) hipLaunchKernelGGL((gemm256r_kernel<1>), g2, dim3(G4_NT), 0, s, q);
-        else if (cm64 == 4) hipLaunchKernelGGL((gemm256r_kernel<4>), g2, dim3(G4_NT), 0, s, q);
-        else hipLaunchKernelGGL((gemm256r_kernel<5>), g2, dim3(G4_NT), 0, s, q);
-      } else if (ak && bk) {
-        if (cm == 0) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, 0>), g2, dim3(G4_NT), 0, s, q);
-        else if (cm == 1) hipLaunchKernelGGL((gemm256_kernel<true, true, 1, 0>), g2, dim3(G4_NT), 0, s, q);
-        else if (cm == 4) hipLaunchKernelGGL((gemm256_kernel<true, true, 4, 0>), g2, dim3(G4_NT), 0, s, q);
-        else if (cm == 5) hipLaunchKernelGGL((gemm256_kernel<true, true, 5, 0>), g2, dim3(G4_NT), 0, s, q);
-        else hipLaunchKernelGGL((gemm256_kernel<true, true, -1, -1>), g2, dim3(G4_NT), 0, s, q);
-      } else if (!ak && !bk) {
-        if (q.conv_mode == 3) hipLaunchKernelGGL((gemm256_kernel<false, false, 0, 1>), g2, dim3(G4_NT), 0, s, q);
-        else if (q.conv_mode == 0) hipLaunchKernelGGL((gemm256_kernel<false, false, 0, 0>), g2, dim3(G4_NT), 0, s, q);
-        else hipLaunchKernelGGL((gemm256_kernel<false, false, -1, -1>), g2, dim3(G4_NT), 0, s, q);
-      } else if (ak) {
-        hipLaunchKernelGGL((gemm256_kernel<true, false, -1, -1>), g2, dim3(G4_NT), 0, s, q);
-      } else {
-        hipLaunchKernelGGL((gemm256_kernel<false, true, -1, -1>), g2, dim3(G4_NT), 0, s, q);
-      }
-      FS2_CHECK_LAUNCH();
-      return 0;
-    }
-    // 256x128 tiles down to 60 of them (M = 6400 encoder / predictor GEMMs: 75 tiles beat the
-    // 150 tiles of the 128x128 kernel, e.g. predictor conv fwd 45 -> 31 us); FS2_GEMM_BIG_MIN
-    // overrides for A/B runs
-    static const int big_min = getenv_int("FS2_GEMM_BIG_MIN", 60);
-    const bool use_big = !no_big && p.conv_mode != 2 &&
-                         ((p.vec_ok && p.split_k <= 1 && tiles_big * batch >= big_min) ||
-                          (slices && p.vec_ok && tiles_big * p.split_k >= 160) ||
-                          (wgrad && tiles_big * split_big >= 160));
-    if (use_big) {
-      GemmP q = p;
-      q.g4_flags = getenv_int("FS2_BIG_FLAGS", 0);
-      q.tiles_m = (p.M + BBM - 1) / BBM;
-      if (wgrad) {
-        q.split_k = split_big;
-        q.k_per_split = ((p.K + split_big - 1) / split_big + 63) / 64 * 64;
-        q.split_k = (p.K + q.k_per_split - 1) / q.k_per_split;
-        split_big = q.split_k;
-        q.vec_ok = split_big == 1;
-        q.accumulate = 1;
-      }
-      dim3 g2(q.tiles_m * q.tiles_n, 1, wgrad ? split_big : (slices ? p.split_k : gz));
-      const int cm = conv_variant(q, 64);
-      if (ak && bk) {
-        if (cm == 0) hipLaunchKernelGGL((gemm_big_kernel<true, true, 0, 0>), g2, dim3(BNT), 0, s, q);
-        else if (cm == 1) hipLaunchKernelGGL((gemm_big_kernel<true, true, 1, 0>), g2, dim3(BNT), 0, s, q);
-        else if (cm == 4) hipLaunchKernelGGL((gemm_big_kernel<true, true, 4, 0>), g2, dim3(BNT), 0, s, q);
-        else if (cm == 5) hipLaunchKernelGGL((gemm_big_kernel<true, true, 5, 0>), g2, dim3(BNT), 0, s, q);
-        else hipLaunchKernelGGL((gemm_big_kernel<true, true, -1, -1>), g2, dim3(BNT), 0, s, q);
-      } else if (!ak && !bk) {
-        if (q.conv_mode == 3) hipLaunchKernelGGL((gemm_big_kernel<false, false, 0, 1>), g2, dim3(BNT), 0, s, q);
-        else if (q.conv_mode == 0) hipLaunchKernelGGL((gemm_big_kernel<false, false, 0, 0>), g2, dim3(BNT), 0, s, q);
-        else hipLaunchKernelGGL((gemm_big_kernel<false, false, -1, -1>), g2, dim3(BNT), 0, s, q);
-      } else if (ak) {
-        hipLaunchKernelGGL((gemm_big_kernel<true, false, -1, -1>), g2, dim3(BNT), 0, s, q);
-      } else {
-        hipLaunchKernelGGL((gemm_big_kernel<false, true, -1, -1>), g2, dim3(BNT), 0, s, q);
-      }
-    } else {
-      if (p.conv_mode == 2) launch4<T, false, true>(p, grid, s, ak, bk);
-      else launch4<T, true, true>(p, grid, s, ak, bk);
-    }
-  } else {
-    launch4<T, false, false>(p, grid, s, ak, bk);
-  }
-  FS2_CHECK_LAUNCH();
-  return 0;
+// row of gemm_big_kernel / gemm256_kernel within its block of the table (cm: conv_variant)
+int tile_variant(int ak, int bk, int cm, int conv_mode) {
+  if (ak && bk) return cm == 0 ? 0 : cm == 1 ? 1 : cm == 4 ? 2 : cm == 5 ? 3 : 4;
+  if (!ak && !bk) return conv_mode == 3 ? 5 : conv_mode == 0 ? 6 : 7;
+  return ak ? 8 : 9;
 }
 
 bool aligned16(const void* ptr) { return ((uintptr_t)ptr & 15) == 0; }
 
-}  // namespace
-
-extern "C" int fs2_gemm(const fs2_gemm_desc* d, void* stream) {
+// the argument checks (host): a.p or an FS2_E* code; 1 for an empty problem (nothing to run)
+int validate(const fs2_gemm_desc* d, GemmArgs& a) {
   if (!d || d->M < 0 || d->N < 0 || d->K < 0) return FS2_EINVAL;
-  if (d->M == 0 || d->N == 0) return 0;
+  if (d->M == 0 || d->N == 0) return 1;
   const int es = d->dtype == FS2_BF16 ? 2 : 4;
   const int epc = 16 / es;
   const int bk = 8 * epc;
-  GemmP p{};
+  a = GemmArgs{};
+  GemmP& p = a.p;
   p.M = d->M; p.N = d->N; p.K = d->K;
   p.kvalid = d->kvalid > 0 ? d->kvalid : d->K;
   p.mvalid = d->mvalid > 0 ? min(d->mvalid, d->M) : d->M;
@@ -3207,7 +2944,6 @@ extern "C" int fs2_gemm(const fs2_gemm_desc* d, void* stream) {
                     p.conv_mode || batch > 1 || p.split_k > 1 || p.accumulate || p.c_conv_kw))
     return FS2_EINVAL;
 
-  // ---- argument checks (host) ----
   if (!p.A || !p.B || !p.C) return FS2_EINVAL;
   if (p.K % epc) return FS2_EINVAL;
   if (!aligned16(p.A) || !aligned16(p.B)) return FS2_EALIGN;
@@ -3240,7 +2976,6 @@ extern "C" int fs2_gemm(const fs2_gemm_desc* d, void* stream) {
     }
   }
   if (p.c_conv_kw > 0 && (p.N % p.c_conv_kw)) return FS2_EINVAL;
-  int split_req = p.split_k;
   if (p.split_k > 1) {
     if (!p.c_fp32 || batch > 1) return FS2_EINVAL;
     if (p.split_stride > 0 && (p.accumulate || p.split_stride < (long)(p.mvalid - 1) * p.ldc + p.nvalid))
@@ -3252,31 +2987,292 @@ extern "C" int fs2_gemm(const fs2_gemm_desc* d, void* stream) {
     p.split_k = (nkt + kps - 1) / kps;
   }
   if (p.accumulate && !p.c_fp32) return FS2_EINVAL;
-  {
-    const int oes = p.c_fp32 ? 4 : es;
-    const int ov = 16 / oes;  // output elements per 16 bytes
-    bool v = p.c_conv_kw == 0 && aligned16(p.C) && (p.ldc % 8) == 0;
-    if (batch > 1) v = v && ((p.sC1 | p.sC2) % ov) == 0 && ((p.sR1 | p.sR2) % epc) == 0;
-    if (p.bias) v = v && aligned16(p.bias);
-    if (p.gate) v = v && aligned16(p.gate) && (p.ldg % 8) == 0;
-    if (p.residual) v = v && aligned16(p.residual) && (p.ldr % 8) == 0;
-    v = v && (p.nvalid % 4) == 0;   // 4-column lane groups of the direct epilogue
-    p.vec_align = v;
-    p.vec_ok = v && (p.split_k <= 1 || p.split_stride > 0);
+  const int ov = 16 / (p.c_fp32 ? 4 : es);  // output elements per 16 bytes
+  bool v = p.c_conv_kw == 0 && aligned16(p.C) && (p.ldc % 8) == 0;
+  if (batch > 1) v = v && ((p.sC1 | p.sC2) % ov) == 0 && ((p.sR1 | p.sR2) % epc) == 0;
+  if (p.bias) v = v && aligned16(p.bias);
+  if (p.gate) v = v && aligned16(p.gate) && (p.ldg % 8) == 0;
+  if (p.residual) v = v && aligned16(p.residual) && (p.ldr % 8) == 0;
+  v = v && (p.nvalid % 4) == 0;   // 4-column lane groups of the direct epilogue
+  p.vec_align = v;
+  p.vec_ok = v && (p.split_k <= 1 || p.split_stride > 0);
+  if (p.split_stride > 0 && p.split_k <= 1) p.split_stride = 0;
+  a.dtype = d->dtype; a.ak = d->a_kmajor != 0; a.bk = d->b_kmajor != 0; a.batch = batch;
+  return 0;
+}
+
+// Kernel selection.  Pure: reads a (and, in the experiments build, the FS2_* switches) and
+// writes pl.  The order of the branches is behaviour: w4b, conv_mode 6, ps, pk, 256, big, 128.
+int plan_gemm(const GemmArgs& a, GemmPlan& pl) {
+  const GemmP& p = a.p;
+  const int ak = a.ak, bk = a.bk;
+  const int gz = p.split_k > 1 ? p.split_k : a.batch;
+  pl.p = p;
+  pl.grid = dim3(p.tiles_m * p.tiles_n, 1, gz);
+  GemmP& q = pl.p;
+  const int major = 3 - (2 * ak + bk);   // row within an FS2_K128 group
+  if (a.dtype == FS2_F32) { pl.kernel = K_F32 + major; return 0; }
+  if (a.dtype != FS2_BF16) return FS2_EINVAL;
+  // bf16: LDS-DMA for both operands, except the reflect-fold dgrad operand (register staged)
+  const int k128 = K_128 + (p.conv_mode == 2 ? 0 : 4) + major;
+  static const bool no_big = getenv_flag("FS2_GEMM_NO_BIG");
+  const int tiles_big = ((p.M + BBM - 1) / BBM) * p.tiles_n;
+  const int batch = p.split_k > 1 ? 1 : gz;
+  // weight-gradient GEMMs (fp32 accumulate, no epilogue ops): the big kernel picks its own
+  // K split; split > 1 takes the LDS-staged atomic epilogue (row-contiguous atomics)
+  const bool wgrad = p.split_stride == 0 && p.c_fp32 && (p.accumulate || p.split_k > 1) &&
+                     batch == 1 && !p.gate &&
+                     !p.residual && !p.bias && !p.row_scale && !p.row_scale_post && !p.relu &&
+                     p.c_conv_kw == 0 && p.vec_align;
+  // ~one round (tgt) of blocks, at least 8 K-tiles per slice
+  auto own_split = [&](int tgt, int tiles) {
+    return wgrad ? max(1, min((tgt + tiles - 1) / tiles, (p.K + 63) / 64 / 8)) : 1;
+  };
+  // the kernel's own split replaces the caller's: whole 64-wide K-tiles, atomics into C
+  auto split_wgrad = [&](int split) {
+    q.k_per_split = ((p.K + split - 1) / split + 63) / 64 * 64;
+    q.split_k = (p.K + q.k_per_split - 1) / q.k_per_split;
+    q.vec_ok = q.split_k == 1;
+    q.accumulate = 1;
+  };
+  // fewer K slices halve the fp32 atomics (decoder QKV weight gradient 95 -> 75 us vs two
+  // rounds); FS2_WGRAD_BIG_TARGET overrides for A/B runs
+  static const int tgt = getenv_int("FS2_WGRAD_BIG_TARGET", 240);
+  const int split_big = own_split(tgt, tiles_big);
+  const bool slices = p.split_stride > 0 && p.split_k > 1;  // caller-chosen split, plain stores
+  // persistent 256x128 kernel: short-K plain GEMMs (FS2_GEMM_NO_PK=1 restores the per-tile
+  // kernels for A/B runs); 32-bit buffer offsets must cover A, B, C and the gate/residual
+  static const bool no_pk = getenv_flag("FS2_GEMM_NO_PK");
+  const long lim = 0x7fffffffL;
+  const long crows = p.c_row_t && p.c_row_pad > 0
+                         ? p.mvalid + ((long)p.mvalid / p.c_row_t + 1) * p.c_row_pad
+                         : p.mvalid;
+  const bool pk_fits = (long)p.M * p.lda * 2 < lim && (long)p.N * p.ldb * 2 < lim &&
+                       crows * p.ldc * (p.c_fp32 ? 4 : 2) < lim &&
+                       (long)p.mvalid * (p.gate ? p.ldg : p.ldr) * 2 < lim;
+  // the large-tile kernels address their operands through 32-bit buffer offsets (per batch
+  // entry); operands beyond 2 GiB take the pointer-based 128x128 kernel instead
+  const long a_rows = ak ? (long)(p.conv_mode ? p.M + 2L * p.conv_p : p.M) : (long)min(p.K, p.kvalid);
+  const long b_rows = bk ? (long)p.N : (long)min(p.K, p.kvalid);
+  const bool big_fits = a_rows * p.lda * 2 < lim && b_rows * p.ldb * 2 < lim;
+  // persistent 256 x 256 / 256 x 192 kernel: long-K K-major GEMMs without gate / residual
+  // operands (FS2_GEMM_NO_PS=1 restores the per-tile kernels for A/B runs)
+  static const bool no_ps = getenv_flag("FS2_GEMM_NO_PS");
+  // the 4-wave 128 x 128-per-wave kernel: plain K-major GEMMs with wide outputs and long K
+  // (FS2_GEMM_W4=0 in the experiments build: the 8-wave kernels, for A/B runs)
+  static const bool w4_on = getenv_int("FS2_GEMM_W4", 1) != 0;
+  // K >= 2048 and >= 160 tiles: the decoder conv2 forward (K = 1536) measured 52 vs 49 us on
+  // the short-K persistent kernel, the encoder's (50 tiles of 256 x 192) 43 us
+  static const int w4_min_k = getenv_int("FS2_W4_MIN_K", 2048);
+  static const int w4_min_tiles = getenv_int("FS2_W4_MIN_TILES", 160);
+  // 256 x 256 or 256 x 192 tiles of the w4b / ps kernels: by rounds x width over the 256 CUs
+  // (ties to the wider tile)
+  const int tm256 = (p.M + 255) / 256, tn256 = (p.N + 255) / 256, tn192 = (p.N + 191) / 192;
+  const int t256 = tm256 * tn256, t192 = tm256 * tn192;
+  const bool w192 = (long)((t192 + 255) / 256) * 192 < (long)((t256 + 255) / 256) * 256;
+  const long a_ext = ak ? (long)(p.M - 1) * p.lda + p.K : 0;
+  const long b_ext = bk ? (long)(p.N - 1) * p.ldb + p.K : 0;
+  const bool w4 = w4_on && ak && bk && p.conv_mode == 0 && batch == 1 && p.split_k <= 1 &&
+                  !p.accumulate && !p.gate && !p.residual && !p.row_scale && !p.row_scale_post &&
+                  p.K % 128 == 0 && p.K >= (p.a_kw ? 256 : max(256, w4_min_k)) &&
+                  (p.a_kw || (p.N >= 384 && p.M >= 2048)) &&
+                  p.nvalid % 4 == 0 && p.ldc % 4 == 0 && p.vec_align &&
+                  a_ext * 2 < 0x7fffffffL && b_ext * 2 < 0x7fffffffL &&
+                  ((long)p.M + 257) * p.lda * 2 < 0x7fffffffL &&
+                  ((long)p.N + 257) * p.ldb * 2 < 0x7fffffffL;
+  if (p.a_kw && !w4) return FS2_EINVAL;   // the tap-inner order exists on this kernel only
+  if (w4 && ((w192 ? t192 : t256) >= w4_min_tiles || p.a_kw)) {
+    q.tiles_m = tm256;
+    q.tiles_n = w192 ? tn192 : tn256;
+    q.a_bytes = (int)(a_ext * 2), q.b_bytes = (int)(b_ext * 2);
+    q.g4_flags = getenv_int("FS2_W4_FLAGS", 0);
+    pl.grid = dim3(q.tiles_m * q.tiles_n);
+    pl.kernel = K_W4B + (w192 ? 0 : 2) + (p.c_fp32 ? 0 : 1);
+    return 0;
   }
-  hipStream_t s0 = (hipStream_t)stream;
-  if (p.split_stride > 0) {
-    // slices the shortened split leaves unwritten read as zero
-    const int oes = p.c_fp32 ? 4 : es;
-    for (int z = max(p.split_k, 1); z < split_req; ++z)
-      if (hipMemset2DAsync(p.C + (long)z * p.split_stride * oes, p.ldc * oes, 0,
-                           (size_t)p.nvalid * oes, p.mvalid, s0) != hipSuccess)
-        return FS2_EINVAL;
-    if (p.split_k <= 1) p.split_stride = 0;
+  if (p.conv_mode == 6) {
+    if (!p.vec_align) return FS2_EALIGN;
+    q.g4_flags = getenv_int("FS2_PS_FLAGS", 0);
+    q.tiles_m = tm256, q.tiles_n = tn256;
+    const int nu = q.tiles_m * q.tiles_n * max(1, p.split_k);
+    if (nu > 1024) return FS2_EINVAL;   // one unit per block (gemm_ps_kernel BT)
+    pl.grid = dim3((nu + 7) / 8 * 8);
+    pl.kernel = K_PS6;
+    return 0;
   }
-  const int gz = p.split_k > 1 ? p.split_k : batch;
+  // FS2_PS_MODES: bit 0 plain, bit 1 reflect conv (fwd), bit 2 padded-domain conv (dgrad).
+  // Default 5: in the bench step the unsplit decoder conv1 data gradient gains 0.15-0.2 ms,
+  // while the conv1 forward measured 0-0.1 ms slower than gemm256_kernel (A/B runs).
+  // Short K (256 <= K < 2048) when the tiles fill at least 200 of the 256 CUs: the decoder's
+  // N = 384 / 1152 projections and FFN conv2 forward (M = 31264; tools/pk_bench.py: conv2 fwd
+  // 63.8 -> 49.1 us, out_proj 29.1 -> 22.0, in_proj 65.6 -> 52.6); the encoder's 25-row-tile
+  // shapes stay on the per-tile kernels (ps 30 -> 43 us).  FS2_PS_MIN_K / FS2_PS_SHORT_TILES
+  // override for A/B runs.
+  static const int ps_modes = getenv_int("FS2_PS_MODES", 5);
+  static const int ps_min_k = getenv_int("FS2_PS_MIN_K", 256);
+  static const int ps_short_tiles = getenv_int("FS2_PS_SHORT_TILES", 200);
+  const int cm_ps = p.conv_mode == 0 ? 0
+                    : ((p.conv_mode == 1 || p.conv_mode == 4) && p.conv_dil == 1 && p.conv_c % 64 == 0
+                           ? p.conv_mode : -1);
+  const bool ps_on = cm_ps >= 0 && (ps_modes >> (cm_ps == 0 ? 0 : (cm_ps == 1 ? 1 : 2))) & 1;
+  // a gate / residual operand (plain A only) takes the 256 x 192 instance (its register budget;
+  // a 256 x 128 one, free of the spills of this one, measured slower: decoder gated dgrad
+  // 105-110 -> 120-122 us, step 18.05-18.11 -> 18.23-18.25 ms, tools/r04_eo.sh)
+  const bool ps_op = p.gate || p.residual;
+  const bool ps_w192 = ps_op || w192;
+  const int ps_nt = ps_w192 ? t192 : t256;
+  // a padded-domain output (c_row_t) exists only on this kernel: it takes every such GEMM
+  const bool ps_k = p.K >= 2048 || (p.K >= max(ps_min_k, 128) && ps_nt >= ps_short_tiles) ||
+                    (p.c_row_t && p.K >= 128);
+  const bool ps_go = !no_ps && ak && bk && ps_on && batch == 1 && p.split_k <= 1 && p.vec_ok &&
+      !p.accumulate && !(p.gate && p.residual) && (!ps_op || cm_ps == 0) && p.relu <= 1 && ps_k &&
+      p.N >= 128 && pk_fits;
+  if (p.c_row_t && !ps_go) return FS2_EINVAL;
+  if (!ps_go && !big_fits) { pl.kernel = k128; return 0; }
+  if (ps_go) {
+    q.g4_flags = getenv_int("FS2_PS_FLAGS", 0);
+    q.tiles_m = tm256;
+    q.tiles_n = ps_w192 ? tn192 : tn256;
+    const int nt = q.tiles_m * q.tiles_n;
+    const int cus = p.max_ctas;
+    pl.grid = dim3(nt < cus ? (nt + 7) / 8 * 8 : cus);
+    const int v = cm_ps == 0 ? 0 : cm_ps == 1 ? 1 : 2;
+    pl.kernel = K_PS + (ps_w192 ? (ps_op ? 0 : 1 + v) : 4 + v);
+    return 0;
+  }
+  // narrow outputs with K >= 1152 (FFN conv2 forward, QKV data gradient) measured faster
+  // on the per-tile 256x128 kernel: decoder 70.5 -> 63.6 and 58.3 -> 55.6 us, encoder
+  // 33.7 -> 29.5 and 32.7 -> 29.0 (tools/gemm_bench.py, FS2_GEMM_NO_PK A/B);
+  // FS2_PK_NARROW=1 keeps them on the persistent kernel
+  static const bool pk_narrow = getenv_flag("FS2_PK_NARROW");
+  const bool pk_shape = p.K <= 768 || p.N > 512 || pk_narrow;
+  const bool pk_ok = !no_pk && ak && bk && p.conv_mode == 0 && batch == 1 && p.split_k <= 1 &&
+                     p.vec_ok && !p.accumulate && !(p.gate && p.residual) && p.K > 64 && pk_fits;
+  // tile of the persistent short-K kernel: 256 x 128 where those tiles fill most of a round
+  // (the decoder's shapes that gemm_ps_kernel does not take); below 160 such tiles (the
+  // encoder / predictor shapes, M = 6400) 128 x 128 or 128 x 64 tiles, whichever finishes in
+  // fewer per-CU tile-areas (two 128 x 64 blocks share a CU) -- K up to 4096 there, since the
+  // per-tile 256 x 128 kernel that takes the narrow long-K shapes fills 75 of the 256 CUs.
+  // FS2_PK_CFG = 44 / 24 / 22 forces one for A/B runs.
+  int pk_cfg = 0;
+  if (pk_ok) {
+    const long t44 = (long)((p.M + 255) / 256) * ((p.N + 127) / 128);
+    const long t24 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
+    const long t22 = (long)((p.M + 127) / 128) * ((p.N + 63) / 64);
+    // per-CU work in 128 x 128 tile units over the rounds each needs (ties: larger tile)
+    const long c44 = (t44 + 255) / 256 * 2, c24 = (t24 + 255) / 256, c22 = (t22 + 511) / 512;
+    long best = 1L << 40;
+    if (p.K <= 1536 && pk_shape) { pk_cfg = 44; best = c44; }
+    if (t44 < 400 && p.K <= 4096) {
+      if (c24 < best) { pk_cfg = 24; best = c24; }
+      if (c22 < best) { pk_cfg = 22; best = c22; }
+    }
+    static const int force = getenv_int("FS2_PK_CFG", 0);
+    if (force == 44 || force == 24 || force == 22) pk_cfg = force;
+  }
+  if (pk_cfg) {
+    q.g4_flags = getenv_int("FS2_PK_FLAGS", 0);
+    const int TM = pk_cfg == 44 ? 256 : 128, TN = pk_cfg == 22 ? 64 : 128;
+    q.tiles_m = (p.M + TM - 1) / TM;
+    q.tiles_n = (p.N + TN - 1) / TN;
+    const int nt = q.tiles_m * q.tiles_n;
+    const int slots = (pk_cfg == 22 ? 2 : 1) * p.max_ctas;   // blocks resident at once (LDS)
+    // >= 8 blocks: every XCD chunk needs a block (blocks with no tile exit at once)
+    pl.grid = dim3(nt < slots ? (nt + 7) / 8 * 8 : slots);
+    pl.kernel = K_PK + (pk_cfg == 44 ? 0 : pk_cfg == 24 ? 1 : 2);
+    return 0;
+  }
+  // 256x256 phased kernel: wide outputs (< 10 % column padding; the QKV projection's
+  // N = 1152 pads 11 % and measured 100 vs 85 us on the 256x128 kernel at M = 31264)
+  static const bool no256 = getenv_flag("FS2_GEMM_NO256");
+  const bool wide = p.N >= 512 && tn256 * 256 * 100 <= p.N * 110;
+  const int split256 = own_split(240, t256);
+  // from 150 tiles: the encoder FFN conv1 forward (M = 6400, N = 1536: 150 tiles of 256^2 in
+  // one round vs 300 of 256x128 in 1.2 rounds) 122 -> 112 us; FS2_G4_MIN_TILES overrides
+  static const int g4_min = getenv_int("FS2_G4_MIN_TILES", 150);
+  const bool use256 = !no256 && wide && p.conv_mode != 2 &&
+                      ((p.vec_ok && p.split_k <= 1 && t256 * batch >= g4_min) ||
+                       (slices && p.vec_ok && t256 * p.split_k >= 160) ||
+                       (wgrad && t256 * split256 >= 160));
+  if (use256) {
+    q.g4_flags = getenv_int("FS2_G4_FLAGS", 0);
+    q.tiles_m = tm256, q.tiles_n = tn256;
+    if (wgrad) split_wgrad(split256);
+    pl.grid = dim3(t256, 1, wgrad ? q.split_k : (slices ? p.split_k : gz));
+    // full-row regions (gemm256r_kernel) for K-major A and B with 64-aligned taps;
+    // FS2_G4R=0 (experiments build) keeps gemm256_kernel
+    static const bool g4r = getenv_int("FS2_G4R", 1) != 0;
+    const int cm64 = conv_variant(q, 64);
+    if (ak && bk && g4r && cm64 >= 0) {
+      // register-direct epilogue (TR): bf16 output, no gate, one K split, 8-column granules
+      static const bool g4tr = getenv_int("FS2_G4R_TR", 1) != 0;
+      const bool tr = g4tr && q.vec_ok && !q.c_fp32 && !q.gate && q.split_k <= 1 &&
+                      q.nvalid % 8 == 0 && q.ldc % 8 == 0 && (!q.residual || q.ldr % 8 == 0) &&
+                      (q.relu <= 1) && !q.accumulate;
+      pl.kernel = K_256R + (tr && cm64 <= 1 ? cm64 : 2 + (cm64 == 0 ? 0 : cm64 == 1 ? 1 : cm64 == 4 ? 2 : 3));
+    } else {
+      pl.kernel = K_256 + tile_variant(ak, bk, conv_variant(q, 32), q.conv_mode);
+    }
+    return 0;
+  }
+  // 256x128 tiles down to 60 of them (M = 6400 encoder / predictor GEMMs: 75 tiles beat the
+  // 150 tiles of the 128x128 kernel, e.g. predictor conv fwd 45 -> 31 us); FS2_GEMM_BIG_MIN
+  // overrides for A/B runs
+  static const int big_min = getenv_int("FS2_GEMM_BIG_MIN", 60);
+  const bool use_big = !no_big && p.conv_mode != 2 &&
+                       ((p.vec_ok && p.split_k <= 1 && tiles_big * batch >= big_min) ||
+                        (slices && p.vec_ok && tiles_big * p.split_k >= 160) ||
+                        (wgrad && tiles_big * split_big >= 160));
+  if (!use_big) { pl.kernel = k128; return 0; }
+  q.g4_flags = getenv_int("FS2_BIG_FLAGS", 0);
+  q.tiles_m = (p.M + BBM - 1) / BBM;
+  if (wgrad) split_wgrad(split_big);
+  pl.grid = dim3(q.tiles_m * q.tiles_n, 1, wgrad ? q.split_k : (slices ? p.split_k : gz));
+  pl.kernel = K_BIG + tile_variant(ak, bk, conv_variant(q, 64), q.conv_mode);
+  return 0;
+}
+
+// what fs2_gemm returns before it launches; 1: an empty problem, nothing to run
+int plan(const fs2_gemm_desc* d, GemmArgs& a, GemmPlan& pl) {
+  const int rc = validate(d, a);
+  return rc ? rc : plan_gemm(a, pl);
+}
+
+int launch(const GemmPlan& pl, hipStream_t s) {
+  const GemmKernel& k = KERNELS[pl.kernel];
+  hipLaunchKernelGGL(k.fn, pl.grid, dim3(k.block), 0, s, pl.p);
+  FS2_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int fs2_gemm(const fs2_gemm_desc* d, void* stream) {
+  GemmArgs a;
+  GemmPlan pl;
+  if (const int rc = plan(d, a, pl)) return rc < 0 ? rc : 0;
   hipStream_t s = (hipStream_t)stream;
-  if (d->dtype == FS2_BF16) return launch_gemm<bf16>(p, gz, s, d->a_kmajor, d->b_kmajor);
-  if (d->dtype == FS2_F32) return launch_gemm<float>(p, gz, s, d->a_kmajor, d->b_kmajor);
-  return FS2_EINVAL;
+  // slices the shortened split leaves unwritten read as zero
+  const int oes = a.p.c_fp32 ? 4 : (a.dtype == FS2_BF16 ? 2 : 4);
+  if (d->split_stride > 0)
+    for (int z = a.p.split_k; z < d->split_k; ++z)
+      if (hipMemset2DAsync(a.p.C + (long)z * d->split_stride * oes, a.p.ldc * oes, 0,
+                           (size_t)a.p.nvalid * oes, a.p.mvalid, s) != hipSuccess)
+        return FS2_EINVAL;
+  return launch(pl, s);
+}
+
+extern "C" int fs2_gemm_plan(const fs2_gemm_desc* d, fs2_gemm_plan_info* out) {
+  if (!out) return FS2_EINVAL;
+  *out = fs2_gemm_plan_info{};
+  GemmArgs a;
+  GemmPlan pl;
+  if (const int rc = plan(d, a, pl)) return rc < 0 ? rc : 0;
+  std::strncpy(out->kernel, KERNELS[pl.kernel].name, sizeof(out->kernel) - 1);
+  out->grid[0] = (int)pl.grid.x; out->grid[1] = (int)pl.grid.y; out->grid[2] = (int)pl.grid.z;
+  out->block = KERNELS[pl.kernel].block;
+  out->tiles_m = pl.p.tiles_m; out->tiles_n = pl.p.tiles_n;
+  out->split_k = pl.p.split_k; out->k_per_split = pl.p.k_per_split;
+  out->vec_ok = pl.p.vec_ok; out->accumulate = pl.p.accumulate;
+  return 0;
 }

@@ -68,6 +68,14 @@ class GemmDesc(ctypes.Structure):
     ]
 
 
+class GemmPlanInfo(ctypes.Structure):
+    _fields_ = [
+        ("kernel", ctypes.c_char * 64), ("grid", ctypes.c_int * 3), ("block", ctypes.c_int),
+        ("tiles_m", ctypes.c_int), ("tiles_n", ctypes.c_int), ("split_k", ctypes.c_int),
+        ("k_per_split", ctypes.c_int), ("vec_ok", ctypes.c_int), ("accumulate", ctypes.c_int),
+    ]
+
+
 class LossDesc(ctypes.Structure):
     _fields_ = [
         ("B", ctypes.c_int), ("Tm", ctypes.c_int), ("Tp", ctypes.c_int), ("NM", ctypes.c_int),
@@ -105,6 +113,7 @@ Fl = ctypes.c_float
 # name -> (restype, argtypes); must match include/fs2_hip.h exactly
 SIGNATURES = {
     "fs2_gemm": (I, [ctypes.POINTER(GemmDesc), P]),
+    "fs2_gemm_plan": (I, [ctypes.POINTER(GemmDesc), ctypes.POINTER(GemmPlanInfo)]),
     "fs2_colsum": (I, [P, I64, I, I, I, P, I, P, P]),
     "fs2_conv_fold": (I, [P, I, I64, I, I, I, I, P, I64, P, I64, P, P, I, P]),
     "fs2_colsum_workspace_floats": (I64, [I, I]),

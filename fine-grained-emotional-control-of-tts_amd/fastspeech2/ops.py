@@ -38,12 +38,24 @@ def round_up(x, m):
     return (x + m - 1) // m * m
 
 
-# FS2_GEMM_TRACE=1: count fs2_gemm calls by (shape, operand flags, calling engine line); the
-# table is printed to stderr at exit (tools/gemm_sites.sh) -- which call sites take which kernel
+# FS2_GEMM_TRACE=1: count fs2_gemm calls by (shape, operand flags, kernel and grid from
+# fs2_gemm_plan, calling engine line); the table is printed to stderr at exit
+# (tools/gemm_sites.sh) -- which call sites take which kernel
 _TRACE = collections.Counter() if os.environ.get("FS2_GEMM_TRACE") else None
 
+GemmPlan = collections.namedtuple(
+    "GemmPlan", "kernel grid block tiles_m tiles_n split_k k_per_split vec_ok accumulate")
 
-def _trace(d, conv):
+
+def _plan(d):
+    """fs2_gemm_plan of a descriptor: what fs2_gemm would launch (host only, no GPU work)"""
+    i = N.GemmPlanInfo()
+    _chk(N.lib().fs2_gemm_plan(ctypes.byref(d), ctypes.byref(i)), "fs2_gemm_plan")
+    return GemmPlan(i.kernel.decode(), tuple(i.grid), i.block, i.tiles_m, i.tiles_n, i.split_k,
+                    i.k_per_split, i.vec_ok, i.accumulate)
+
+
+def _trace(d):
     f = sys._getframe(2)
     while f is not None and os.path.basename(f.f_code.co_filename) == "ops.py":
         f = f.f_back
@@ -52,14 +64,15 @@ def _trace(d, conv):
                                    ("B", d.bias), ("r", d.relu), ("g", d.gate), ("R", d.residual),
                                    ("s", d.row_scale), ("S", d.row_scale_post),
                                    ("+", d.accumulate), ("c", d.c_row_t)) if v)
-    _TRACE[(d.M, d.N, d.K, conv[0] if conv else 0, d.split_k, d.batch, flags, site)] += 1
+    pl = _plan(d)
+    _TRACE[(d.M, d.N, d.K, d.conv_mode, d.split_k, d.batch, flags, pl.kernel, pl.grid, site)] += 1
 
 
 def _trace_dump():
     for k, n in sorted(_TRACE.items(), key=lambda x: -x[0][0] * x[0][1] * x[0][2] * x[1]):
-        M, N_, K, cm, sk, b, fl, site = k
+        M, N_, K, cm, sk, b, fl, kern, grid, site = k
         print(f"gemm {n:4d}x M {M:6d} N {N_:5d} K {K:6d} conv {cm} split {sk} batch {b:4d} "
-              f"[{fl}] {site}", file=sys.stderr)
+              f"[{fl}] {kern} grid {grid[0]}x{grid[2]} {site}", file=sys.stderr)
 
 
 if _TRACE is not None:
@@ -71,7 +84,8 @@ def gemm(M, N_, K, A, lda, B, ldb, C, ldc, *, dt, a_kmajor=1, b_kmajor=1, conv=N
          c_conv_kw=0, bias=None, relu=0, gate=None, ldg=0, row_scale=None, residual=None, ldr=0,
          row_scale_post=None, accumulate=0, split_k=1, split_stride=0, kvalid=0, mvalid=0,
          nvalid=0, batch=1, batch_div=1, strides=None, conv_dil=1, c_row=None, max_ctas=0,
-         a_kw=0, k_eff=None):
+         a_kw=0, k_eff=None, plan=False):
+    """fs2_gemm.  plan=True (gemm_plan): launch nothing and return the GemmPlan of this call."""
     d = N.GemmDesc()
     d.k_eff = _p(k_eff)       # conv_mode 6: device int32, effective K of token-compacted images
     d.conv_dil = conv_dil
@@ -94,9 +108,18 @@ def gemm(M, N_, K, A, lda, B, ldb, C, ldc, *, dt, a_kmajor=1, b_kmajor=1, conv=N
     d.batch, d.batch_div = batch, batch_div
     if strides is not None:
         (d.sA1, d.sA2, d.sB1, d.sB2, d.sC1, d.sC2, d.sR1, d.sR2) = strides
+    if plan:
+        return _plan(d)
     if _TRACE is not None:
-        _trace(d, conv)
+        _trace(d)
     _chk(N.lib().fs2_gemm(ctypes.byref(d), _s()), "fs2_gemm")
+
+
+def gemm_plan(*args, **kw):
+    """Which kernel a gemm(...) call with these arguments takes: GemmPlan(kernel, grid, ...),
+    kernel as the profiler prints the instantiation.  Host only; tensors may be replaced by
+    any 16-byte-aligned address (they are not read)."""
+    return gemm(*args, plan=True, **kw)
 
 
 def conv_fold(Xpad, B, T, P, C, out, ldo, *, dt, residual=None, ldr=0, row_scale=None,

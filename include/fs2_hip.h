@@ -110,6 +110,23 @@ typedef struct fs2_gemm_desc {
 
 int fs2_gemm(const fs2_gemm_desc* d, void* stream);
 
+/* What fs2_gemm would do with a descriptor, decided on the host without any launch: the kernel
+ * (the instantiation as a profiler prints it, e.g. "gemm_ps_kernel<0, 48, 1, 0>"; the 128 x 128
+ * kernel reads "gemm_kernel<bf16|float, AK, BKM, GA, GB>"), its grid in blocks and block size,
+ * and the tiling / split the kernel receives.  Returns what fs2_gemm would return before
+ * launching (0 or an FS2_E* code); an empty problem (M or N = 0) returns 0 with kernel "".
+ * The descriptor's pointers are only tested for NULL and 16-byte alignment, never followed.  */
+typedef struct fs2_gemm_plan_info {
+  char kernel[64];
+  int grid[3];
+  int block;
+  int tiles_m, tiles_n;
+  int split_k, k_per_split;
+  int vec_ok, accumulate;
+} fs2_gemm_plan_info;
+
+int fs2_gemm_plan(const fs2_gemm_desc* d, fs2_gemm_plan_info* out);
+
 /* reflect-padding adjoint + dgrad epilogue (K16): Xpad fp32 [B][T+2P][C] from conv_mode 4
  * (nsplit split-K slices split_stride floats apart, summed here; nsplit <= 1: one slice),
  *   out[b,s] = ((Xpad[s+P] + Xpad[P-s]{1<=s<=P} + Xpad[2(T-1)-s+P]{T-1-P<=s<=T-2}) * rs

@@ -20,6 +20,16 @@ def rel(a, b):
     return ((a - b).abs().max() / b.abs().max().clamp(min=1e-12)).item()
 
 
+def gemm_on(kernel, *args, **kw):
+    """ops.gemm(*args, **kw), after asserting that the dispatcher takes ``kernel`` (the
+    instantiation as a profiler prints it) for exactly these arguments: a test written for one
+    kernel fails when a threshold change moves its shapes to another.  ops.gemm_plan is a host
+    call (fs2_gemm_plan), no GPU work."""
+    from fastspeech2 import ops
+    assert ops.gemm_plan(*args, **kw).kernel == kernel
+    ops.gemm(*args, **kw)
+
+
 @pytest.mark.parametrize("dt,code,tol", DT)
 def test_gemm_epilogue(cuda, dt, code, tol):
     from fastspeech2 import ops
@@ -581,13 +591,22 @@ def test_conv_fold_vector_form_bit_exact(cuda, split):
 
 @pytest.mark.parametrize("Bn,T", [(32, 640), (1, 640), (32, 200), (32, 977)])
 def test_gemm_big_tile_paths_bf16(cuda, Bn, T):
-    """BASELINE-sized GEMMs that take the 256x128 LDS-DMA kernel (gemm_big_kernel): implicit
-    reflect conv k=9 forward with bias+ReLU, zero-padded shift-conv data gradient + fold, and
-    the weight gradient into the [O][KW][C] layout -- split-K with atomics at Bn=32, the
-    single-split vector accumulate epilogue at Bn=1; T=200 (encoder) takes the split-slice
-    data gradient; T=977 is the bench's decoder shape (M = 31264: a partial last 256-row tile,
-    utterance boundaries inside tiles).  bf16 inputs, fp32 reference on the same
-    bf16 values, rel 2e-2."""
+    """BASELINE-sized implicit convs on the large-tile kernels (asserted per call, the
+    table below): reflect conv k=9 forward with bias+ReLU (gemm256r_kernel's register-direct epilogue;
+    the 128x128 kernel at Bn=1), zero-padded shift-conv data gradient + fold (the persistent
+    padded-domain kernel; T=200, the encoder, takes the split-slice data gradient on
+    gemm_big_kernel), and the weight gradient into the [O][KW][C] layout -- the kernel's own
+    split-K with atomics on gemm256_kernel at Bn=32, gemm_big_kernel at Bn=1; T=977 is the
+    bench's decoder shape (M = 31264: a partial last 256-row tile, utterance boundaries inside
+    tiles).  bf16 inputs, fp32 reference on the same bf16 values, rel 2e-2."""
+    k128, psd = "gemm_kernel<bf16, true, true, true, true>", "gemm_ps_kernel<4, 48, 0, 0>"
+    fwd, dgrad, wgrad = {
+        (32, 640): ("gemm256r_kernel<1, true, 64>", psd, "gemm256_kernel<false, false, 0, 1>"),
+        (1, 640): (k128, k128, "gemm_big_kernel<false, false, 0, 1>"),
+        (32, 200): ("gemm256r_kernel<1, true, 64>", "gemm_big_kernel<true, true, 4, 0>",
+                    "gemm256_kernel<false, false, 0, 1>"),
+        (32, 977): ("gemm256r_kernel<1, true, 64>", psd, "gemm256_kernel<false, false, 0, 1>"),
+    }[(Bn, T)]
     from fastspeech2 import ops
     torch.manual_seed(Bn)
     Cin, O, KW = 384, 1536, 9
@@ -605,21 +624,21 @@ def test_gemm_big_tile_paths_bf16(cuda, Bn, T):
     G = torch.randn(out.shape, device=cuda).to(torch.bfloat16).contiguous()
     pre.backward(G.float())          # data/weight gradients of the conv itself (no ReLU gate)
     Y = torch.empty(M, O, device=cuda, dtype=torch.bfloat16)
-    ops.gemm(M, O, KW * Cin, X, Cin, Wf, KW * Cin, Y, O, dt=1, conv=(1, T, KW, Cin), bias=bias,
-             relu=1)
+    gemm_on(fwd, M, O, KW * Cin, X, Cin, Wf, KW * Cin, Y, O, dt=1, conv=(1, T, KW, Cin), bias=bias,
+            relu=1)
     assert rel(Y, out.detach().reshape(-1, O)) < 2e-2
     Mp = Bn * (T + 2 * P)
     from fastspeech2.engine import dgrad_split
     split = dgrad_split(Mp, Cin, KW * O, 1)
     Xpad = torch.empty(split, Mp, Cin, device=cuda)
-    ops.gemm(Mp, Cin, KW * O, G, O, Wb, KW * O, Xpad, Cin, dt=1, conv=(4, T, KW, O), c_fp32=1,
-             split_k=split, split_stride=Mp * Cin if split > 1 else 0)
+    gemm_on(dgrad, Mp, Cin, KW * O, G, O, Wb, KW * O, Xpad, Cin, dt=1, conv=(4, T, KW, O), c_fp32=1,
+            split_k=split, split_stride=Mp * Cin if split > 1 else 0)
     dX = torch.empty(M, Cin, device=cuda, dtype=torch.bfloat16)
     ops.conv_fold(Xpad, Bn, T, P, Cin, dX, Cin, dt=1, nsplit=split, split_stride=Mp * Cin)
     assert rel(dX, Xr.grad.reshape(-1, Cin)) < 2e-2
     dW = torch.full((O, KW, Cin), 0.5, device=cuda)        # accumulates onto existing values
-    ops.gemm(O, KW * Cin, ops.round_up(M, 8), G, O, X, Cin, dW, KW * Cin, dt=1, a_kmajor=0,
-             b_kmajor=0, conv=(3, T, KW, Cin), c_fp32=1, kvalid=M, accumulate=1)
+    gemm_on(wgrad, O, KW * Cin, ops.round_up(M, 8), G, O, X, Cin, dW, KW * Cin, dt=1, a_kmajor=0,
+            b_kmajor=0, conv=(3, T, KW, Cin), c_fp32=1, kvalid=M, accumulate=1)
     assert rel(dW - 0.5, Wr.grad.permute(0, 2, 1)) < 2e-2
 
 
@@ -629,10 +648,10 @@ def test_gemm_big_tile_paths_bf16(cuda, Bn, T):
 def test_wgrad_conv3_slices(cuda, Bn, T, O, Cin, KW, ns):
     """Implicit-reflect-conv weight gradients written as split-K fp32 planes (split_stride, the
     engine's path for the large FFN / PostNet weights) -- the 256x256 MN-major kernel
-    (gemm256_kernel<false, false, 0, 1>) at the decoder / encoder FFN conv1 shapes, a
-    PostNet-like k=5 shape, and
-    ragged ones (M, N not multiples of 256, utterance boundaries inside K-tiles, a slice count
-    that leaves no plane empty and one plane (ns = 1)).  The summed planes equal the fp32
+    (gemm256_kernel<false, false, 0, 1>) at the decoder / encoder FFN conv1 shapes; a
+    PostNet-like k=5 shape and ragged ones (M, N not multiples of 256, utterance boundaries
+    inside K-tiles, a slice count that leaves no plane empty and one plane (ns = 1)) stay on
+    the 128x128 kernel (too few 256x256 tiles).  The summed planes equal the fp32
     reference of the same bf16 values (rel 2e-2); planes cover every output element exactly."""
     from fastspeech2 import ops
     torch.manual_seed(T + O)
@@ -652,9 +671,11 @@ def test_wgrad_conv3_slices(cuda, Bn, T, O, Cin, KW, ns):
     K = ops.round_up(M, 8)
     stride = O * KW * Cin
     ws = torch.full((ns, O, KW * Cin), float("nan"), device=cuda)
-    ops.gemm(O, KW * Cin, K, G, O, X, Cin, ws, KW * Cin, dt=1, a_kmajor=0, b_kmajor=0,
-             conv=(3, T, KW, Cin), c_fp32=1, kvalid=M, nvalid=KW * Cin, split_k=ns,
-             split_stride=stride if ns > 1 else 0)
+    kernel = ("gemm256_kernel<false, false, 0, 1>" if (O, Cin) == (1536, 384)
+              else "gemm_kernel<bf16, false, false, true, true>")
+    gemm_on(kernel, O, KW * Cin, K, G, O, X, Cin, ws, KW * Cin, dt=1, a_kmajor=0, b_kmajor=0,
+            conv=(3, T, KW, Cin), c_fp32=1, kvalid=M, nvalid=KW * Cin, split_k=ns,
+            split_stride=stride if ns > 1 else 0)
     torch.cuda.synchronize()
     assert torch.isfinite(ws).all()
     assert rel(ws.sum(0), ref) < 2e-2
@@ -709,8 +730,8 @@ def test_wgrad_kmajor_padded_images(cuda, Bn, T, O, Cin, KW, S):
     assert torch.equal(dYT.reshape(O, Kp), yi)
     stride = O * KW * Cin
     ws = torch.full((S, O, KW * Cin), float("nan"), device=cuda)
-    ops.gemm(O, KW * Cin, Kp, dYT, Kp, XT, Kp, ws, KW * Cin, dt=1, conv=(6, T, KW, Cin),
-             c_fp32=1, split_k=S, split_stride=stride if S > 1 else 0)
+    gemm_on("gemm_ps_kernel<0, 64, 0, 1>", O, KW * Cin, Kp, dYT, Kp, XT, Kp, ws, KW * Cin, dt=1,
+            conv=(6, T, KW, Cin), c_fp32=1, split_k=S, split_stride=stride if S > 1 else 0)
     torch.cuda.synchronize()
     assert torch.isfinite(ws).all()
     assert rel(ws.sum(0), ref) < 1e-3
@@ -739,8 +760,18 @@ def test_gemm_persistent_long_k(cuda, M, N, K, c32):
     """Long-K K-major GEMMs take the persistent 256 x 256 / 256 x 192 kernel (gemm_ps_kernel):
     both tile widths, partial row / column tiles, a partial last K-tile (K = 2056), bf16 and
     fp32 outputs, the bias + ReLU + row-scale epilogue; fp32 reference on the same bf16 values.
-    The last three: the encoder FFN conv1 shape as a plain GEMM (one round of 200 tiles), 16
-    tiles at K = 8192, and a ragged one (partial rows, columns and last K-tile)."""
+    Among them the encoder FFN conv1 shape as a plain GEMM (one round of 200 tiles) and 16
+    tiles at K = 8192.  The ragged (5000, 700, 3000) (partial rows, columns and last K-tile; K
+    not a multiple of 16, so no vector epilogue) runs on the 128 x 128 kernel.  Without the
+    row scales the wide shapes with M >= 2048 and K % 128 == 0 move to the 4-wave kernel."""
+    ps48, ps64, k128 = ("gemm_ps_kernel<0, 48, 0, 0>", "gemm_ps_kernel<0, 64, 0, 0>",
+                        "gemm_kernel<bf16, true, true, true, true>")
+    scaled, plain = {
+        (1000, 1536, 2048): (ps48, ps48), (31264, 1536, 3456): (ps64, "gemm_w4b_kernel<false, 8>"),
+        (700, 384, 4096): (ps48, ps48), (300, 200, 2056): (ps48, ps48),
+        (6400, 1536, 3456): (ps48, "gemm_w4b_kernel<false, 6>"), (2000, 384, 8192): (ps48, ps48),
+        (5000, 700, 3000): (k128, k128), (10752, 1536, 2048): (ps64, "gemm_w4b_kernel<false, 8>"),
+    }[(M, N, K)]
     from fastspeech2 import ops
     torch.manual_seed(M + N)
     A = torch.randn(M, K, device=cuda).to(torch.bfloat16)
@@ -750,13 +781,13 @@ def test_gemm_persistent_long_k(cuda, M, N, K, c32):
     rs2 = torch.rand(M, device=cuda) + 0.5
     ref = torch.relu(A.float() @ W.float().t() + bias) * rs[:, None] * rs2[:, None]
     C = torch.full((M, N), float("nan"), device=cuda, dtype=torch.float32 if c32 else torch.bfloat16)
-    ops.gemm(M, N, K, A, K, W, K, C, N, dt=1, c_fp32=c32, bias=bias, relu=1, row_scale=rs,
-             row_scale_post=rs2)
+    gemm_on(scaled, M, N, K, A, K, W, K, C, N, dt=1, c_fp32=c32, bias=bias, relu=1, row_scale=rs,
+            row_scale_post=rs2)
     assert torch.isfinite(C.float()).all()
     assert rel(C, ref) < 1e-2
     # plain (no epilogue operands), output written with a row pitch > N
     C2 = torch.zeros(M, N + 8, device=cuda, dtype=torch.bfloat16)
-    ops.gemm(M, N, K, A, K, W, K, C2, N + 8, dt=1)
+    gemm_on(plain, M, N, K, A, K, W, K, C2, N + 8, dt=1)
     assert rel(C2[:, :N], A.float() @ W.float().t()) < 1e-2
     assert (C2[:, N:] == 0).all()
 
@@ -796,8 +827,10 @@ def test_gemm_four_wave(cuda, M, N, K, c32, crow):
         rows, keep = (m // L) * crow[0] + m % L, (m % L) < crow[0]
         nrows = (M // L + 1) * crow[0]
     C = torch.full((nrows, N), float("nan"), device=cuda, dtype=odt)
-    ops.gemm(M, N, K, A, K, W, K, C, N, dt=1, c_fp32=c32, bias=bias, relu=1,
-             **({"c_row": crow} if crow else {}))
+    # 256 x 192 tiles (NF = 6) where they need no more rounds x width than 256 x 256 ones
+    kernel = f"gemm_w4b_kernel<{'true' if c32 else 'false'}, {8 if N in (1536, 1000) and M > 30000 else 6}>"
+    gemm_on(kernel, M, N, K, A, K, W, K, C, N, dt=1, c_fp32=c32, bias=bias, relu=1,
+            **({"c_row": crow} if crow else {}))
     torch.cuda.synchronize()
     written = torch.zeros(nrows, dtype=torch.bool, device=cuda)
     written[rows[keep]] = True
@@ -836,7 +869,11 @@ def test_gemm_persistent_short_k(cuda, M, N, K, op):
         x = x * rs[:, None]
     ref = x * rs2[:, None]
     C = torch.full((M, N), float("nan"), device=cuda, dtype=torch.bfloat16)
-    ops.gemm(M, N, K, A, K, W, K, C, N, dt=1, bias=bias, row_scale=rs, row_scale_post=rs2, **kw)
+    # gate / residual: the 256 x 192 operand instance; else the tile width by rounds x width
+    kernel = ("gemm_ps_kernel<0, 48, 1, 0>" if op else
+              "gemm_ps_kernel<0, 64, 0, 0>" if N == 1152 else "gemm_ps_kernel<0, 48, 0, 0>")
+    gemm_on(kernel, M, N, K, A, K, W, K, C, N, dt=1, bias=bias, row_scale=rs, row_scale_post=rs2,
+            **kw)
     torch.cuda.synchronize()
     assert torch.isfinite(C.float()).all()
     assert rel(C, ref) < 1e-2
@@ -847,10 +884,12 @@ def test_gemm_persistent_short_k(cuda, M, N, K, op):
                                           (6400, 384, 776, None, 0), (31264, 80, 384, None, 0),
                                           (31264, 384, 80, "residual", 0), (5000, 200, 3000, "gate", 1)])
 def test_gemm_persistent_small_tiles(cuda, M, N, K, op, c32):
-    """The persistent short-K kernel's 128 x 128 / 128 x 64 tile instances (round 4), which the
-    dispatcher picks below 160 tiles of 256 x 128 (the encoder / predictor / concat / mel-linear
-    shapes, M = 6400 or N = 80): bias + row scales + gate or residual epilogues, partial row /
-    column / K tiles, bf16 and fp32 outputs; fp32 reference on the same bf16 values, rel 1e-2."""
+    """The persistent short-K kernel (gemm_pk_kernel) at the encoder / predictor / concat /
+    mel-linear shapes (M = 6400 or N = 80): its 128 x 128 tile instance <2, 4>, and the
+    256 x 128 one <4, 4> at N = 768 / 1152 -- no shape here reaches the 128 x 64 instance
+    <2, 2>.  Bias + row scales + gate or residual epilogues, partial row / column / K tiles,
+    bf16 and fp32 outputs; fp32 reference on the same bf16 values, rel 1e-2.  The ragged
+    (5000, 200, 3000) with a gate runs on the long-K persistent kernel's operand instance."""
     from fastspeech2 import ops
     torch.manual_seed(M + N + K + 7)
     A = torch.randn(M, K, device=cuda).to(torch.bfloat16)
@@ -872,8 +911,10 @@ def test_gemm_persistent_small_tiles(cuda, M, N, K, op, c32):
     ref = x * rs2[:, None]
     C = torch.full((M, N), float("nan"), device=cuda,
                    dtype=torch.float32 if c32 else torch.bfloat16)
-    ops.gemm(M, N, K, A, K, W, K, C, N, dt=1, c_fp32=c32, bias=bias, row_scale=rs,
-             row_scale_post=rs2, **kw)
+    kernel = ("gemm_ps_kernel<0, 48, 1, 0>" if K == 3000 else
+              "gemm_pk_kernel<4, 4>" if N in (768, 1152) else "gemm_pk_kernel<2, 4>")
+    gemm_on(kernel, M, N, K, A, K, W, K, C, N, dt=1, c_fp32=c32, bias=bias, row_scale=rs,
+            row_scale_post=rs2, **kw)
     torch.cuda.synchronize()
     assert torch.isfinite(C.float()).all()
     assert rel(C, ref) < 1e-2
@@ -882,14 +923,20 @@ def test_gemm_persistent_small_tiles(cuda, M, N, K, op, c32):
 def test_gemm_grid_budget(cuda):
     """fs2_gemm_desc.max_ctas: persistent GEMMs given a grid budget (the weight-gradient side
     stream's GEMMs run at 208 blocks) walk more tiles per block and give results bit-identical
-    to the full-grid launch, for the long-K (gemm_ps_kernel) and short-K (gemm_pk_kernel,
-    128-row and 256-row tiles) instances, on any stream; out-of-range budgets mean the full
-    grid (8 is the floor).  The budget is per call: the library keeps no per-stream state."""
+    to the full-grid launch, for gemm_ps_kernel (256-row tiles) and gemm_pk_kernel (128-row
+    tiles), on any stream; out-of-range budgets mean the full grid (8 is the floor).  The 4-wave
+    kernel that takes the first shape is not persistent: one block per tile whatever the
+    budget.  The budget is per call: the library keeps no per-stream state."""
     from fastspeech2 import ops
     torch.manual_seed(11)
-    shapes = [(31264, 1536, 3456), (31264, 1152, 384), (6400, 384, 1152)]
+    shapes = [(31264, 1536, 3456, "gemm_w4b_kernel<false, 8>", {c: 738 for c in (0, 64, 208, 3, 300)}),
+              (31264, 1152, 384, "gemm_ps_kernel<0, 48, 0, 0>", {0: 256, 64: 64, 208: 208, 3: 8, 300: 256}),
+              (6400, 384, 1152, "gemm_pk_kernel<2, 4>", {0: 152, 64: 64, 208: 152, 3: 8, 300: 152})]
     s_side = torch.cuda.Stream()
-    for M, N, K in shapes:
+    for M, N, K, kernel, blocks in shapes:
+        for ctas, nb in blocks.items():
+            pl = ops.gemm_plan(M, N, K, 4096, K, 4096, K, 4096, N, dt=1, bias=4096, relu=1, max_ctas=ctas)
+            assert (pl.kernel, pl.grid) == (kernel, (nb, 1, 1))
         A = torch.randn(M, K, device=cuda).to(torch.bfloat16)
         W = (torch.randn(N, K, device=cuda) * 0.05).to(torch.bfloat16)
         bias = torch.randn(N, device=cuda)
@@ -915,10 +962,12 @@ def test_gemm_grid_budget(cuda):
                                          (31264, 1536, 3456, (1, 977, 9, 384)),
                                          (31264, 384, 13824, (4, 977, 9, 1536)), (200, 80, 384, None)])
 def test_gemm_nan_passes_without_activation(cuda, M, N, K, conv):
-    """A NaN input row comes out NaN through every bf16 GEMM kernel family when the epilogue
-    has no activation (persistent short-K, 256x128, 256x256 implicit conv, persistent long-K
-    padded-domain conv, 128x128): the epilogue's 'no activation' is a select, not a max
-    against -inf, so NaN-based divergence checks still see the NaN."""
+    """A NaN input row comes out NaN through the bf16 GEMM kernel families when the epilogue
+    has no activation (persistent 256-row gemm_ps_kernel, persistent short-K gemm_pk_kernel at
+    two sizes, 256x256 implicit conv gemm256r_kernel, persistent padded-domain conv): the
+    epilogue's 'no activation' is a select, not a max against -inf, so NaN-based divergence
+    checks still see the NaN.  No shape here reaches the 256x128 or the 128x128
+    kernel."""
     from fastspeech2 import ops
     torch.manual_seed(K)
     if conv is not None and conv[0] == 4:
@@ -934,7 +983,10 @@ def test_gemm_nan_passes_without_activation(cuda, M, N, K, conv):
         lda = A.shape[1]
     W = (torch.randn(N, K, device=cuda) * 0.05).to(torch.bfloat16)
     C = torch.zeros(M, N, device=cuda, dtype=torch.bfloat16)
-    ops.gemm(M, N, K, A, lda, W, K, C, N, dt=1, conv=conv)
+    kernel = {(1152, None): "gemm_ps_kernel<0, 48, 0, 0>", (384, None): "gemm_pk_kernel<2, 4>",
+              (80, None): "gemm_pk_kernel<2, 4>", (1536, 1): "gemm256r_kernel<1, true, 64>",
+              (384, 4): "gemm_ps_kernel<4, 48, 0, 0>"}[(N, conv[0] if conv else None)]
+    gemm_on(kernel, M, N, K, A, lda, W, K, C, N, dt=1, conv=conv)
     torch.cuda.synchronize()
     nan_rows = torch.isnan(C.float()).any(1).nonzero().flatten().tolist()
     assert nan_rows, "the NaN input did not reach the output"
@@ -943,7 +995,8 @@ def test_gemm_nan_passes_without_activation(cuda, M, N, K, conv):
 
 
 def test_gemm_short_k_two_streams(cuda):
-    """The persistent short-K kernel (gemm_pk_kernel) under concurrency: 40 back-to-back
+    """The persistent kernels with a gate operand (gemm_ps_kernel's operand instance,
+    gemm_pk_kernel) and the per-tile 256x128 kernel at K = 64 under concurrency: 40 back-to-back
     launches alternating between two streams (different tile counts, nk = 1 and nk = 6, bias
     + ReLU-gate epilogue) each cover every tile exactly once -- equal to the first launch of
     the shape and to the fp32 reference on the same bf16 values.  (A per-stream dynamic tile
@@ -951,14 +1004,16 @@ def test_gemm_short_k_two_streams(cuda):
     stalls the block once per tile.)"""
     from fastspeech2 import ops
     torch.manual_seed(3)
-    shapes = [(31264, 1152, 384), (6400, 384, 1536), (3000, 1536, 64)]
+    shapes = [(31264, 1152, 384, "gemm_ps_kernel<0, 48, 1, 0>"), (6400, 384, 1536, "gemm_pk_kernel<2, 4>"),
+              (3000, 1536, 64, "gemm_big_kernel<true, true, 0, 0>")]
     data = []
-    for M, N, K in shapes:
+    for M, N, K, kernel in shapes:
         A = torch.randn(M, K, device=cuda).to(torch.bfloat16)
         W = (torch.randn(N, K, device=cuda) * 0.05).to(torch.bfloat16)
         bias = torch.randn(N, device=cuda)
         G = torch.randn(M, N, device=cuda).to(torch.bfloat16)
         ref = torch.where(G.float() > 0, A.float() @ W.float().t() + bias, 0.0)
+        assert ops.gemm_plan(M, N, K, A, K, W, K, G, N, dt=1, bias=bias, gate=G, ldg=N).kernel == kernel
         data.append((M, N, K, A, W, bias, G, ref))
     s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
     s1.wait_stream(torch.cuda.current_stream())

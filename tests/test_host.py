@@ -79,6 +79,85 @@ def test_gemm_host_validation_rejects_bad_args():
     assert lib.fs2_loss_fwd_bwd(None, None) == -1
 
 
+def _gemm_plan_cases():
+    """(descriptor on a 16-byte-aligned host buffer, recorded answer) for every case of
+    tests/golden/gemm_plans.json (sweep) and gemm_plan_sites.npz (call sites), the dispatcher's
+    decisions recorded from commit 10745b4"""
+    import json
+    import numpy as np
+    from fastspeech2 import _native as N
+    golden = os.path.join(ROOT, "tests", "golden")
+    fx = json.load(open(os.path.join(golden, "gemm_plans.json")))
+    assert fx["recorded_from"] == "10745b4"
+    fields = dict(N.GemmDesc._fields_)
+    assert fx["desc_fields"] == list(fields)
+    sites = np.load(os.path.join(golden, "gemm_plan_sites.npz"))
+    rows = list(zip(sites["desc"].tolist(), sites["ans"].tolist()))
+    for sp, *ans in fx["sweep"]:
+        r = list(fx["desc_defaults"])
+        for i, v in zip(sp[::2], sp[1::2]):
+            r[i] = v
+        rows.append((r, ans))
+    buf = (ctypes.c_char * 64)()
+    base = (ctypes.addressof(buf) + 15) // 16 * 16
+    cases = []
+    for r, (rc, k, *rest) in rows:
+        d = N.GemmDesc()
+        for (name, ty), v in zip(d._fields_, r):
+            if ty is not ctypes.c_void_p:
+                setattr(d, name, v)
+            elif v >= 0:                            # -1 = NULL: absent
+                setattr(d, name, base + v)
+        cases.append((d, (rc, fx["kernels"][k] if k >= 0 else "", *rest)))
+    return buf, cases
+
+
+def test_gemm_plan_matches_recorded():
+    """fs2_gemm_plan returns, for every recorded descriptor, the code, kernel, grid, block and
+    rewritten tiling / split fields the dispatcher of commit 10745b4 chose (recorded at its
+    launch points): the bench step's and the GPU suite's call sites, a sample of a 50 000
+    descriptor sweep with every reachable instantiation and error return, and pairs on either
+    side of the thresholds"""
+    from fastspeech2 import _native as N
+    lib = N.load()
+    buf, cases = _gemm_plan_cases()
+    assert len(cases) > 2500 and len({a[1] for _, a in cases}) >= 48
+    for d, want in cases:
+        i = N.GemmPlanInfo()
+        rc = lib.fs2_gemm_plan(ctypes.byref(d), ctypes.byref(i))
+        got = (rc, i.kernel.decode(), *i.grid, i.block, i.tiles_m, i.tiles_n, i.split_k,
+               i.k_per_split, i.vec_ok, i.accumulate)
+        assert got == want, {n: getattr(d, n) for n, _ in d._fields_ if getattr(d, n)}
+
+
+def test_gemm_plan_agrees_with_gemm_on_errors():
+    """fs2_gemm and fs2_gemm_plan return the same code for every recorded descriptor that was
+    refused (fs2_gemm returns before any launch there)"""
+    from fastspeech2 import _native as N
+    lib = N.load()
+    buf, cases = _gemm_plan_cases()
+    bad = [(d, a[0]) for d, a in cases if a[0] != 0]
+    assert {rc for _, rc in bad} == {-1, -2} and len(bad) > 50
+    for d, rc in bad:
+        assert lib.fs2_gemm(ctypes.byref(d), None) == rc
+        assert lib.fs2_gemm_plan(ctypes.byref(d), ctypes.byref(N.GemmPlanInfo())) == rc
+
+
+def test_gemm_plan_is_pure():
+    """planning twice gives identical output and leaves the descriptor untouched"""
+    from fastspeech2 import _native as N
+    lib = N.load()
+    buf, cases = _gemm_plan_cases()
+    for d, _ in cases[::7]:
+        before = bytes(d)
+        a, b = N.GemmPlanInfo(), N.GemmPlanInfo()
+        ctypes.memset(ctypes.byref(b), 0xff, ctypes.sizeof(b))      # every byte of the output is written
+        assert lib.fs2_gemm_plan(ctypes.byref(d), ctypes.byref(a)) == \
+            lib.fs2_gemm_plan(ctypes.byref(d), ctypes.byref(b))
+        assert bytes(a) == bytes(b) and bytes(d) == before
+    assert lib.fs2_gemm_plan(ctypes.byref(cases[0][0]), None) == -1
+
+
 def test_attention_host_validation_rejects_bad_args():
     """fs2_attn_fwd / fs2_attn_bwd / fs2_softmax_fwd / fs2_softmax_bwd return before any launch
     on bad arguments.  Every call here must be refused: one that passed the checks would launch."""
