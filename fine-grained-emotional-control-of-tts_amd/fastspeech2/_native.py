@@ -163,6 +163,10 @@ SIGNATURES = {
     "fs2_intensity_input": (I, [P, I, I, I, I, P, I, I, P]),
     "fs2_intensity_head": (I, [P, I64, P, P, P, P, P, I, I, I, I, P, I, P]),
     "fs2_phoneme_average": (I, [P, I, I, P, P, I, I, P, P]),
+    "fs2_rank_mixup_input": (I, [P, P, P, I, I, I, P, I, I, P]),
+    "fs2_rank_pool": (I, [P, P, P, I, I, I, P, P, P]),
+    "fs2_rank_loss_fwd": (I, [P, P, P, P, P, P, P, P, I, I, Fl, Fl, P, P]),
+    "fs2_bucket_means": (I, [P, P, P, P, P, I, I, I, P, P]),
     "fs2_collate_phonemes": (I, [P, P, P, P, I, I, P, P, P, P]),
     "fs2_collate_frames": (I, [P, P, P, P, P, I, I, I, P, P, P, P, P, P]),
     "fs2_vocoder_input": (I, [P, I, I, I, I, P, I, I, P]),

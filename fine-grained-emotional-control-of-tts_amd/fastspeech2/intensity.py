@@ -5,8 +5,10 @@ Reference:
 * ``IntensityExtractor``  -- emo_rank_tts/rank_model/model.py:56-109 (input projection :71,
   ``nn.TransformerEncoder`` of ``ConvTransformerEncoderLayer`` :8-50 / :74-75, emotion
   embedding :78, classifier :81, mask :84-93, forward :96-109);
-* ``RankModel`` container -- rank_model/model.py:115-135 (``rank_model.intensity_extractor`` is
-  what fastspeech2/train.py:218-221 loads and freezes);
+* ``RankModel`` -- rank_model/model.py:115-166 (``rank_model.intensity_extractor`` is what
+  fastspeech2/train.py:218-221 loads and freezes; its eval forward :138-166 -- mixup staging
+  ``fs2_rank_mixup_input``, ONE extractor pass over the 2B mixed sequences, pooling and score
+  ``fs2_rank_pool`` -- feeds ``fastspeech2.rank``: validation losses and the prototype bank);
 * ``get_intensity_representation`` -- fastspeech2/train.py:16-51.
 
 The modules here are parameter containers with the reference's attribute names, so
@@ -110,9 +112,11 @@ class IntensityExtractor(nn.Module):
 
 
 class RankModel(nn.Module):
-    """Parameter container of rank_model/model.py:115-135 so reference RankModel checkpoints load
-    (``rank_model.load_state_dict(...)``, train.py:218-221).  Only ``.intensity_extractor`` is on
-    the FastSpeech2 train path; the rank-model training forward is out of scope."""
+    """rank_model/model.py:115-166 with the reference's attribute names, so its checkpoints load
+    (``rank_model.load_state_dict(...)``, train.py:218-221).  ``.intensity_extractor`` is what
+    the FastSpeech2 train path uses; ``forward`` runs in eval mode only (validation losses and
+    the prototype bank, ``fastspeech2.rank``).  Rank-model training is out of scope (DESIGN.md
+    section 7)."""
 
     def __init__(self, n_mels, n_heads, n_emotions, n_encoder_layers, hidden_dim, kernel_size,
                  dropout, act_dtype=torch.float32, **kwargs):
@@ -123,9 +127,46 @@ class RankModel(nn.Module):
                                                       dropout, act_dtype=act_dtype)
         self.projector = nn.Linear(n_emotions, 1, bias=False)
 
-    def forward(self, *args, **kwargs):
-        raise NotImplementedError("rank-model training is outside the FastSpeech2 train path "
-                                  "(DESIGN.md section 7); use .intensity_extractor")
+    @torch.no_grad()
+    def forward(self, emo_X, neu_X, emotions, length, lambdas=None):
+        """Eval forward of rank_model/model.py:138-166.  emo_X, neu_X (B, T, n_mels+2) on the
+        HIP device, emotions (B,) ids, length (B,) valid frames (>= 1: the pooling divides by
+        it), lambdas (2, B) or None (sampled from Beta(1, 1) as in :144-146).  Returns
+        ``(lam_i, lam_j, Ii, Ij, hi, hj, ri, rj)`` of shapes (B,1,1), (B,1,1), (B,T,E), (B,T,E),
+        (B,E), (B,E), (B,), (B,); everything but the lambdas is fp32 on the device, without an
+        autograd graph.
+
+        Both mixes go through the extractor as one batch of 2B sequences.  As in the reference,
+        ``h`` sums I over ALL T frames of the padded batch (padded frames hold the classifier
+        bias) and divides by ``length``, so ``h`` and ``r`` depend on the batch's padded
+        length."""
+        if self.training:
+            raise NotImplementedError("rank-model training is outside the FastSpeech2 train path "
+                                      "(DESIGN.md section 7); call .eval() for the evaluation "
+                                      "forward, or use .intensity_extractor")
+        if emo_X.device.type != "cuda" or neu_X.device.type != "cuda":
+            raise RuntimeError("RankModel runs only on the HIP device (libfs2_hip.so); there is "
+                               "no CPU path")
+        B, T, _ = emo_X.shape
+        dev = emo_X.device
+        if lambdas is None:
+            lambdas = torch.distributions.Beta(1.0, 1.0).sample((2, B)).to(dev)   # :144-146
+        lam_i = lambdas[0].unsqueeze(1).unsqueeze(1)
+        lam_j = lambdas[1].unsqueeze(1).unsqueeze(1)
+        eng = self.intensity_extractor.engine()
+        E = self.n_emotions
+        length = length.to(device=eng.dev, dtype=torch.int64)
+        emotions = emotions.to(device=eng.dev, dtype=torch.int64)
+        if length.shape != (B,) or emotions.shape != (B,):
+            raise RuntimeError(f"length and emotions must be ({B},)")
+        len2 = length.repeat(2)
+        X0, B2, _ = eng.stage_mixup(emo_X, neu_X, lambdas)
+        I = eng.forward_staged(X0, B2, T, len2, emotions.repeat(2))           # :156-157
+        h = torch.empty(B2, E, dtype=torch.float32, device=eng.dev)
+        r = torch.empty(B2, dtype=torch.float32, device=eng.dev)
+        Wp = self.projector.weight.detach().float().reshape(-1).contiguous()
+        ops.rank_pool(I, len2, Wp, B2, T, E, h, r)                           # :160-164
+        return lam_i, lam_j, I[:B], I[B:], h[:B], h[B:], r[:B], r[B:]
 
 
 class ExtractorEngine:
@@ -203,10 +244,13 @@ class ExtractorEngine:
                  strides=(H * T * ldt, T * ldt, T * 3 * D, dh, T * D, dh, 0, 0))
 
     def forward(self, x, length, emotions, layout="BTC"):
-        ext = self.x
-        self.prepare()
-        D, H, E = ext.hidden, ext.n_heads, ext.n_emotions
-        C = ext.n_mels + 2
+        X0, B, T = self.stage_input(x, layout)
+        return self.forward_staged(X0, B, T, length, emotions)
+
+    def stage_input(self, x, layout="BTC"):
+        """x fp32 (B,T,C) / (B,C,T) -> the input projection's GEMM rows X0 [B*T][ldx] in the
+        activation dtype.  Returns (X0, B, T)."""
+        C = self.x.n_mels + 2
         if layout not in ("BTC", "BCT"):
             raise ValueError(f"layout must be 'BTC' or 'BCT', got {layout!r}")
         x = x.to(device=self.dev, dtype=torch.float32).contiguous()
@@ -217,13 +261,40 @@ class ExtractorEngine:
         if Cx != C:
             raise RuntimeError(f"extractor input has {Cx} channels, expected n_mels + 2 = {C} "
                                f"(layout={layout})")
+        ldx = round_up(C, self.epc)
+        X0 = self.empty(B * T, ldx)
+        ops.intensity_input(x, int(layout == "BCT"), B, T, C, X0, ldx, dt=self.dt)
+        return X0, B, T
+
+    def stage_mixup(self, emo_X, neu_X, lambdas):
+        """rank_model/model.py:148-153: emo_X, neu_X fp32 (B,T,C) and lambdas fp32 (2,B) -> the
+        GEMM rows of the 2B mixed sequences (lam_i's B first, then lam_j's).  Returns
+        (X0, 2B, T)."""
+        C = self.x.n_mels + 2
+        emo_X = emo_X.to(device=self.dev, dtype=torch.float32).contiguous()
+        neu_X = neu_X.to(device=self.dev, dtype=torch.float32).contiguous()
+        B, T, Cx = emo_X.shape
+        if Cx != C or neu_X.shape != emo_X.shape:
+            raise RuntimeError(f"rank-model inputs must both be (B, T, n_mels + 2 = {C}), got "
+                               f"{tuple(emo_X.shape)} and {tuple(neu_X.shape)}")
+        lambdas = lambdas.to(device=self.dev, dtype=torch.float32).contiguous()
+        if lambdas.shape != (2, B):
+            raise RuntimeError(f"lambdas must be (2, {B}), got {tuple(lambdas.shape)}")
+        ldx = round_up(C, self.epc)
+        X0 = self.empty(2 * B * T, ldx)
+        ops.rank_mixup_input(emo_X, neu_X, lambdas, B, T, C, X0, ldx, dt=self.dt)
+        return X0, 2 * B, T
+
+    def forward_staged(self, X0, B, T, length, emotions):
+        """The extractor from staged input rows X0 [B*T][ldx] on: I (B, T, E) fp32."""
+        ext = self.x
+        self.prepare()
+        D, H, E = ext.hidden, ext.n_heads, ext.n_emotions
         length = length.to(device=self.dev, dtype=torch.int64).contiguous()
         emotions = emotions.to(device=self.dev, dtype=torch.int64).contiguous()
         M = B * T
         P = self.p
-        ldx = round_up(C, self.epc)
-        X0 = self.empty(M, ldx)
-        ops.intensity_input(x, int(layout == "BCT"), B, T, C, X0, ldx, dt=self.dt)
+        ldx = X0.shape[1]
         key_pad = torch.empty(M, dtype=torch.uint8, device=self.dev)
         ops.keypad_from_lengths(length, B, T, key_pad)                  # model.py:84-93
         X = self.empty(M, D)

@@ -398,6 +398,27 @@ def phoneme_average(I, T, E, durations, phon_len, B, Tp, out):
                                      _s()), "fs2_phoneme_average")
 
 
+def rank_mixup_input(emo_X, neu_X, lambdas, B, T, C, X, ldx, *, dt):
+    _chk(N.lib().fs2_rank_mixup_input(_p(emo_X), _p(neu_X), _p(lambdas), B, T, C, _p(X), ldx, dt,
+                                      _s()), "fs2_rank_mixup_input")
+
+
+def rank_pool(I, length, Wp, B, T, E, h, r):
+    _chk(N.lib().fs2_rank_pool(_p(I), _p(length), _p(Wp), B, T, E, _p(h), _p(r), _s()),
+         "fs2_rank_pool")
+
+
+def rank_loss_fwd(lam_i, lam_j, hi, hj, ri, rj, y_emo, y_neu, B, E, alpha, beta, out):
+    _chk(N.lib().fs2_rank_loss_fwd(_p(lam_i), _p(lam_j), _p(hi), _p(hj), _p(ri), _p(rj),
+                                   _p(y_emo), _p(y_neu), B, E, alpha, beta, _p(out), _s()),
+         "fs2_rank_loss_fwd")
+
+
+def bucket_means(frames, order, cstart, utt_off, grp_off, G, K, E, out):
+    _chk(N.lib().fs2_bucket_means(_p(frames), _p(order), _p(cstart), _p(utt_off), _p(grp_off),
+                                  G, K, E, _p(out), _s()), "fs2_bucket_means")
+
+
 def collate_phonemes(order, offsets, phonemes, durations, B, Tp, phon_out, dur_out, in_len):
     _chk(N.lib().fs2_collate_phonemes(_p(order), _p(offsets), _p(phonemes), _p(durations), B, Tp,
                                       _p(phon_out), _p(dur_out), _p(in_len), _s()),

@@ -430,6 +430,39 @@ int fs2_phoneme_average(const float* I, int T, int E, const int64_t* durations,
                         const int64_t* phon_len, int B, int Tp, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Rank-model evaluation path (rank_model/model.py:138-166 in eval mode, loss.py:36-55,
+ * inference.py:98-114).  The extractor runs once over the 2B mixed sequences staged by
+ * fs2_rank_mixup_input.  Every reduction below has a fixed order and uses no atomics.
+ * ------------------------------------------------------------------------------------------ */
+/* emo_X, neu_X fp32 (B,T,C), lambdas fp32 (2,B) -> GEMM rows X[2*B*T][ldx] in dtype: rows
+ * [0, B*T) = lam_i*emo + (1-lam_i)*neu, rows [B*T, 2*B*T) the same with lam_j (two fp32
+ * products and one add, not fused), columns >= C zero.                                       */
+int fs2_rank_mixup_input(const float* emo_X, const float* neu_X, const float* lambdas, int B,
+                         int T, int C, void* X, int ldx, int dtype, void* stream);
+/* h[b,e] = (sum over ALL T frames of I[b,t,e]) / float(length[b]) (padded frames hold the
+ * classifier bias and are summed, as model.py:160 does); r[b] = sum_e h[b,e] * Wp[e].
+ * I fp32 (B,T,E), E <= 8, length[b] >= 1.                                                    */
+int fs2_rank_pool(const float* I, const int64_t* length, const float* Wp, int B, int T, int E,
+                  float* h, float* r, void* stream);
+/* out[0..2] = (alpha*L_mixup + beta*L_rank, L_mixup, L_rank) of loss.py:36-55: the four
+ * batch-mean cross entropies of hi / hj (B,E) against y_emo / y_neu, weighted by the
+ * per-sample lambdas and averaged; L_rank with sigmoid(ri-rj), log(p + 1e-8) and
+ * lam_diff = (lam_i-lam_j+1)/2.  A target outside [0,E) gives NaN.  One block, fp32.        */
+int fs2_rank_loss_fwd(const float* lam_i, const float* lam_j, const float* hi, const float* hj,
+                      const float* ri, const float* rj, const int64_t* y_emo,
+                      const int64_t* y_neu, int B, int E, float alpha, float beta, float* out,
+                      void* stream);
+/* out[g,k,:] = mean of bucket k of group g's frames (inference.py:98-114).  order[grp_off[g] ..
+ * grp_off[g+1]) are the group's utterances in ascending score order; cstart[j] (j = 0..U) is
+ * the number of frames before sorted utterance j; utterance u's frames are rows
+ * [utt_off[u], ...) of frames fp32 [.][E].  The group's N concatenated frames are split as
+ * np.array_split(N, K) does.  fp64 sums in a fixed order, fp32 out.  Empty group: zeros;
+ * empty bucket (N < K): NaN.  E <= 8.                                                        */
+int fs2_bucket_means(const float* frames, const int64_t* order, const int64_t* cstart,
+                     const int64_t* utt_off, const int64_t* grp_off, int G, int K, int E,
+                     float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * GPU collate: TextMelCollateWithAlignment (fastspeech2/dataset.py:62-133) over
  * one packed upload.  Item u's phonemes / durations are [offsets[u], offsets[u+1]) of the
  * packed int64 arrays; its mel is (n_mels, T_u) channel-major at frame_offsets[u] * n_mels,
