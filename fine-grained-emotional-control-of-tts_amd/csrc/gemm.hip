@@ -1944,16 +1944,29 @@ __device__ __forceinline__ void w4_epilogue(const GemmP& p, f32x4 (&acc)[8][NF],
 // slot retired by a counted lgkmcnt) releases the slot's B image, so the B pieces of stage s+2
 // are issued over rows 4-7; then vmcnt (stage s+1 landed), lgkmcnt(0) and the second barrier
 // release the A image, whose pieces of stage s+2 go out over half 1 while the fragments of
-// (s+1, 0) are read.  On the FFN conv1 shape: 344-347 us; issuing all of a stage's DMA at the
-// start of half 1 436 us, two pieces per row over half 1 only (one barrier per stage) 375 us,
-// A and B swapped (the last pieces with 1.5 halves to land instead of 1) 357 us -- the vector
-// memory path's throughput bounds it, not its latency.  Wave-cycles waiting (SQ_WAIT_ANY):
-// 22 % against hipBLASLt's 7 % on the same instruction mix (SQ_ACTIVE_INST_LDS / _VMEM within
-// 10 %), MFMA busy 50 vs 76 %.  Row r of an image holds logical chunk c at
-// physical chunk c ^ (r & 7): conflict-free for the fragment reads' ds_read_b128 lane groups
-// ({0-3, 12-15, 20-27}, ...), and lane-constant for a DMA piece (8 rows x 8 chunks).
+// (s+1, 0) are read.  Row r of an image holds logical chunk c at physical chunk c ^ (r & 7):
+// conflict-free for the fragment reads' ds_read_b128 lane groups ({0-3, 12-15, 20-27}, ...),
+// and lane-constant for a DMA piece (8 rows x 8 chunks).
+// Placement inside a row: every read and every DMA piece sits in the gap behind one MFMA of
+// the row, spread evenly over the row's NF MFMAs and pinned there (sched_barrier): one wave
+// per SIMD issues in order, an MFMA keeps the vector issue port for half of its 16 cycles,
+// and whatever does not fit behind it holds the matrix pipe up.  The earlier form issued a
+// row's three reads and its pieces as one group between two rows; against it, standalone on
+// one box, FFN conv1 forward 330 -> 314, conv1 data gradient 275 -> 256, encoder conv1 72.7
+// -> 66.4 us, outputs bit-identical.
+// Measured and removed: the operands staged through registers instead
+// (buffer_load_dwordx4 into VGPRs, ds_write_b128 into the same image, zero spills): 10 %
+// slower than LDS-DMA with grouped operations and 6 % slower with placed ones -- a
+// ds_write_b128 and a register load cost the lone wave more issue time than the DMA piece
+// they replace; the DMA pieces spread over 12 rows of a stage behind one slot-wide release:
+// equal.  Earlier: all of a stage's DMA at the start of half 1 436 us, two pieces per row
+// over half 1 only (one barrier per stage) 375 us, A and B swapped 357 us, against 344.
+// Wave-cycles waiting (SQ_WAIT_ANY, grouped form): 22 % against hipBLASLt's 7 % on the same
+// instruction mix (SQ_ACTIVE_INST_LDS / _VMEM within 10 %), MFMA busy 50 vs 76 %.
 // FS2_W4_FLAGS (experiments build; results wrong): 1 no barriers, 2 no DMA, 4 no fragment
-// reads -- on the FFN conv1 shape 364 -> 361 / 306 / 331 us, both of the last two 272.
+// reads.  The flags are tested in every gap, which costs the placed loop its gain, so they
+// bound the grouped form only: FFN conv1 forward 352 -> 298 (no DMA) / 298 (no reads) / 256
+// (neither) us, conv1 data gradient 294 -> 264 / 259 / 234 us.
 template <bool C32, int NF>
 __global__ void __launch_bounds__(W4_NT, 1) gemm_w4b_kernel(GemmP p) {
   constexpr int BNW = 32 * NF;                 // block tile columns
@@ -2036,63 +2049,84 @@ __global__ void __launch_bounds__(W4_NT, 1) gemm_w4b_kernel(GemmP p) {
   }
   const int xf = XFLAGS(p);   // experiments build: 1 no barrier, 2 no DMA, 4 no fragment reads
 
+  // A's byte offset of the stage two ahead, advanced by one stage per stage (aoff's division
+  // stays out of the loop): + dn inside a channel chunk, + dw from a chunk's last tap to the
+  // next chunk's first (a plain A: one "tap" per chunk, + 128)
+  const int kwm = p.a_kw ? p.a_kw : 1;
+  const int dn = p.a_kw ? (int)p.lda * 2 : 128, dw = 128 - (kwm - 1) * dn;
+  int ka2 = aoff(2), tap2 = 2 % kwm;
+
   // one stage; SL = its slot (compile-time).  Every stage has the same body: the last two
-  // issue DMA for stages nst, nst+1 (K offsets past the row: bytes of the next row, or zeros
-  // past the operand's extent) into slots no one reads again, and the last reads fragments it
-  // never uses -- a branch-free loop, whose accumulators stay in place across the back edge
+  // issue DMA for stages nst, nst+1 (re-fetching stage 0: K offsets past the operand would not
+  // be range-checked, they ride in soffset) into slots no one reads again, and the last reads
+  // fragments it never uses -- a branch-free loop, whose accumulators stay in place across
+  // the back edge
   auto stage = [&](int s, auto SLc) {
     constexpr int SL = decltype(SLc)::value;
     char* slot = smem + SL * STAGE;
     const char* nslot = smem + (SL ^ 1) * STAGE;
-    // half 0: MFMAs on set 0; reads of this stage's half 1 into set 1, B first (three per
-    // row: B in rows 0-2, A in rows 2-5); a barrier after row 3 (every wave's B reads of this
-    // slot retired: 12 reads issued, NF of them B) releases the slot's B image, whose pieces of
-    // stage s+2 go out over rows 4-7
-    // the last two stages' DMA (into slots no one reads again) re-fetches stage 0: K offsets past
-    // the operand would not be range-checked (soffset)
     const bool live = s + 2 < nst;
-    const int kb = live ? (s + 2) * 128 : 0, ka = live ? aoff(s + 2) : 0;
+    const int kb = live ? (s + 2) * 128 : 0, ka = live ? ka2 : 0;
+    {
+      const bool wrap = ++tap2 == kwm;
+      tap2 = wrap ? 0 : tap2;
+      ka2 += wrap ? dw : dn;
+    }
+    // memory operation k of row i of half H.  k = 0 .. 2: the fragment reads 3 i + k of the
+    // other register set, 16 per half, B first (rows 0-5) -- half 0 reads this stage's half 1,
+    // half 1 reads (s+1, half 0) from the other slot.  k >= 3: the row's DMA pieces of stage
+    // s+2 into this slot: its B pieces over rows 4-7 of half 0, A piece i in row i of half 1
+    auto op = [&](auto Hc, int i, int k) {
+      constexpr int H = decltype(Hc)::value;
+      if (k < 3) {
+        const int r = 3 * i + k;
+        if (xf & 4) return;
+        const char* src = H == 0 ? slot + fl1 : nslot + fl0;
+        if (r < NF) bfr[H ^ 1][r] = *(const bf16x8*)(src + fb + r * 2048);
+        else if (r < NF + 8) af[H ^ 1][r - NF] = *(const bf16x8*)(src + fa + (r - NF) * 2048);
+      } else if (!(xf & 2)) {
+        if (H == 1) {
+          if (k == 3) dma(i, ka, kb, slot);
+        } else if (i >= 4) {
+          int n = 3;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      if (i >= 4 && !(xf & 2)) {
-#pragma unroll
-        for (int t = 0; t < NF; ++t)
-          if (t * 4 / NF == i - 4) dma(8 + t, ka, kb, slot);
-      }
-#pragma unroll
-      for (int j = 0; j < NF; ++j) mfma_acc(acc[i][j], bfr[0][j], af[0][i]);
-      if (!(xf & 4)) {
-#pragma unroll
-        for (int h = 0; h < 3; ++h) {
-          const int r = 3 * i + h;
-          if (r < NF) bfr[1][r] = *(const bf16x8*)(slot + fl1 + fb + r * 2048);
-          else if (r < NF + 8) af[1][r - NF] = *(const bf16x8*)(slot + fl1 + fa + (r - NF) * 2048);
+          for (int t = 0; t < NF; ++t)
+            if (t * 4 / NF == i - 4 && k == n++) dma(8 + t, ka, kb, slot);
         }
       }
-      if (i == 3) {
-        lgkm_wait<12 - NF>();
-        if (!(xf & 1)) __builtin_amdgcn_s_barrier();
+    };
+    // a row's operations one per MFMA gap, spread evenly over its NF MFMAs (the comment above
+    // the kernel), and kept there
+    auto half = [&](auto Hc) {
+      constexpr int H = decltype(Hc)::value;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        int n = 4;   // half 1: three reads and one piece
+        if (H == 0) {
+          n = 3;
+          for (int t = 0; t < NF; ++t) n += (i >= 4 && t * 4 / NF == i - 4) ? 1 : 0;
+        }
+#pragma unroll
+        for (int j = 0; j < NF; ++j) {
+          mfma_acc(acc[i][j], bfr[H][j], af[H][i]);
+#pragma unroll
+          for (int k = 0; k < 5; ++k)
+            if (k < n && k * NF / n == j) op(Hc, i, k);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if (H == 0 && i == 3) {
+          // every wave's B reads of this slot retired (12 reads issued, NF of them B): the
+          // slot's B image is released to the B pieces of stage s+2
+          lgkm_wait<12 - NF>();
+          if (!(xf & 1)) __builtin_amdgcn_s_barrier();
+        }
       }
-    }
+    };
+    half(std::integral_constant<int, 0>{});
     vm_wait<NF>();   // stage s+1 landed; the B pieces of s+2 may be in flight
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this slot's reads done
-    if (!(xf & 1)) __builtin_amdgcn_s_barrier();
-    // half 1: MFMAs on set 1; the A pieces of stage s+2 into this slot, one per row; reads of
-    // (s+1, half 0), B first
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      if (!(xf & 2)) dma(i, ka, kb, slot);
-#pragma unroll
-      for (int j = 0; j < NF; ++j) mfma_acc(acc[i][j], bfr[1][j], af[1][i]);
-      if (!(xf & 4)) {
-#pragma unroll
-        for (int h = 0; h < 3; ++h) {
-          const int r = 3 * i + h;
-          if (r < NF) bfr[0][r] = *(const bf16x8*)(nslot + fl0 + fb + r * 2048);
-          else if (r < NF + 8) af[0][r - NF] = *(const bf16x8*)(nslot + fl0 + fa + (r - NF) * 2048);
-        }
-      }
-    }
+    if (!(xf & 1)) __builtin_amdgcn_s_barrier();         // releases the slot's A image
+    half(std::integral_constant<int, 1>{});
   };
   // two stages per trip (slots 0, 1); K % 128 == 0, so nst is even.  Each trip ends in
   // mfma_drain(): should the compiler copy accumulators on the exit edge, its v_accvgpr reads
