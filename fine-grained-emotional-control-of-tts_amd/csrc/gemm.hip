@@ -2505,14 +2505,8 @@ __global__ void __launch_bounds__(BNT, 1) gemm_ps_kernel(GemmP p) {
       if constexpr (CM == 0) {
         aoff[q] = aval[q] ? ((at_[q] * (int)p.lda + alc[q] * 8) * 2) : BUF_OOB;
       } else {
-        int ts;
-        bool ok = aval[q];
-        if constexpr (CM == 1) {
-          ts = reflect_idx(at_[q] + a_tap - p.conv_p, p.conv_t);
-        } else {
-          ts = at_[q] - a_tap;
-          ok = ok && ts >= 0 && ts < p.conv_t;
-        }
+        const int ts = at_[q] - a_tap;
+        const bool ok = aval[q] && ts >= 0 && ts < p.conv_t;
         aoff[q] = ok ? (((abt[q] + ts) * (int)p.lda + alc[q] * 8) * 2) : BUF_OOB;
       }
     }
@@ -2872,8 +2866,8 @@ struct GemmKernel { const char* name; void (*fn)(GemmP); int block; };
 #define FS2_K128(T, GA, GB)   /* row 3 - (2 * ak + bk) */                                     \
   FS2_K(NT, gemm_kernel<T, true, true, GA, GB>), FS2_K(NT, gemm_kernel<T, true, false, GA, GB>), \
   FS2_K(NT, gemm_kernel<T, false, true, GA, GB>), FS2_K(NT, gemm_kernel<T, false, false, GA, GB>)
-#define FS2_KTILE(K, nt)      /* row tile_variant() */                                         \
-  FS2_K(nt, K<true, true, 0, 0>), FS2_K(nt, K<true, true, 1, 0>), FS2_K(nt, K<true, true, 4, 0>), \
+#define FS2_KTILE(K, nt)      /* row tile_variant() - 1 */                                     \
+  FS2_K(nt, K<true, true, 1, 0>), FS2_K(nt, K<true, true, 4, 0>),                             \
   FS2_K(nt, K<true, true, 5, 0>), FS2_K(nt, K<true, true, -1, -1>),                           \
   FS2_K(nt, K<false, false, 0, 1>), FS2_K(nt, K<false, false, 0, 0>),                         \
   FS2_K(nt, K<false, false, -1, -1>), FS2_K(nt, K<true, false, -1, -1>),                      \
@@ -2883,26 +2877,27 @@ const GemmKernel KERNELS[] = {
     FS2_K(W4_NT, gemm_w4b_kernel<true, 6>), FS2_K(W4_NT, gemm_w4b_kernel<false, 6>),
     FS2_K(W4_NT, gemm_w4b_kernel<true, 8>), FS2_K(W4_NT, gemm_w4b_kernel<false, 8>),
     FS2_K(BNT, gemm_ps_kernel<0, 64, 0, 1>),   // K_PS6: conv_mode 6
-    FS2_K128(bf16, false, true),               // K_128: conv_mode 2
-    FS2_K128(bf16, true, true),                // K_128 + 4: every other bf16 call
-    // K_PS + {0: 192-wide with gate / residual; 1..3: 192-wide, 4..6: 256-wide, conv 0 / 1 / 4}
+    // K_128C2 + (B MN-major): conv_mode 2, whose A is K-major (validate) and register staged
+    FS2_K(NT, gemm_kernel<bf16, true, true, false, true>),
+    FS2_K(NT, gemm_kernel<bf16, true, false, false, true>),
+    FS2_K128(bf16, true, true),                // K_128: every other bf16 call
+    // K_PS + {0: 192-wide with gate / residual; 1, 2: 192-wide, 3, 4: 256-wide, conv 0 / 4}
     FS2_K(BNT, gemm_ps_kernel<0, 48, 1, 0>),
-    FS2_K(BNT, gemm_ps_kernel<0, 48, 0, 0>), FS2_K(BNT, gemm_ps_kernel<1, 48, 0, 0>),
-    FS2_K(BNT, gemm_ps_kernel<4, 48, 0, 0>),
-    FS2_K(BNT, gemm_ps_kernel<0, 64, 0, 0>), FS2_K(BNT, gemm_ps_kernel<1, 64, 0, 0>),
-    FS2_K(BNT, gemm_ps_kernel<4, 64, 0, 0>),
+    FS2_K(BNT, gemm_ps_kernel<0, 48, 0, 0>), FS2_K(BNT, gemm_ps_kernel<4, 48, 0, 0>),
+    FS2_K(BNT, gemm_ps_kernel<0, 64, 0, 0>), FS2_K(BNT, gemm_ps_kernel<4, 64, 0, 0>),
     // K_PK + {0: 256 x 128, 1: 128 x 128, 2: 128 x 64}
     FS2_K(BNT, gemm_pk_kernel<4, 4>), FS2_K(BNT, gemm_pk_kernel<2, 4>), FS2_K(BNT, gemm_pk_kernel<2, 2>),
     // K_256R + {0, 1: register-direct epilogue, conv 0 / 1; 2..5: conv 0 / 1 / 4 / 5}
     FS2_K(G4_NT, gemm256r_kernel<0, true, 64>), FS2_K(G4_NT, gemm256r_kernel<1, true, 64>),
     FS2_K(G4_NT, gemm256r_kernel<0, false, 64>), FS2_K(G4_NT, gemm256r_kernel<1, false, 64>),
     FS2_K(G4_NT, gemm256r_kernel<4, false, 64>), FS2_K(G4_NT, gemm256r_kernel<5, false, 64>),
-    FS2_KTILE(gemm256_kernel, G4_NT),          // K_256
-    FS2_KTILE(gemm_big_kernel, BNT),           // K_BIG
+    // K_256 + tile_variant() - 1: variant 0 (plain, both K-major) is always gemm256r_kernel's
+    FS2_KTILE(gemm256_kernel, G4_NT),
+    FS2_K(BNT, gemm_big_kernel<true, true, 0, 0>), FS2_KTILE(gemm_big_kernel, BNT),   // K_BIG
     FS2_K128(float, false, false),             // K_F32
 };
-enum { K_W4B = 0, K_PS6 = 4, K_128 = 5, K_PS = 13, K_PK = 20, K_256R = 23, K_256 = 29, K_BIG = 39,
-       K_F32 = 49, K_COUNT = 53 };
+enum { K_W4B = 0, K_PS6 = 4, K_128C2 = 5, K_128 = 7, K_PS = 11, K_PK = 16, K_256R = 19, K_256 = 25,
+       K_BIG = 34, K_F32 = 44, K_COUNT = 48 };
 static_assert(sizeof(KERNELS) / sizeof(KERNELS[0]) == K_COUNT, "kernel table out of step");
 
 // what validate makes of a descriptor: the parameter block (128 x 128 tiling, caller's split)
@@ -3048,8 +3043,7 @@ int plan_gemm(const GemmArgs& a, GemmPlan& pl) {
   if (a.dtype == FS2_F32) { pl.kernel = K_F32 + major; return 0; }
   if (a.dtype != FS2_BF16) return FS2_EINVAL;
   // bf16: LDS-DMA for both operands, except the reflect-fold dgrad operand (register staged)
-  const int k128 = K_128 + (p.conv_mode == 2 ? 0 : 4) + major;
-  static const bool no_big = getenv_flag("FS2_GEMM_NO_BIG");
+  const int k128 = p.conv_mode == 2 ? K_128C2 + major : K_128 + major;
   const int tiles_big = ((p.M + BBM - 1) / BBM) * p.tiles_n;
   const int batch = p.split_k > 1 ? 1 : gz;
   // weight-gradient GEMMs (fp32 accumulate, no epilogue ops): the big kernel picks its own
@@ -3070,9 +3064,9 @@ int plan_gemm(const GemmArgs& a, GemmPlan& pl) {
     q.accumulate = 1;
   };
   // fewer K slices halve the fp32 atomics (decoder QKV weight gradient 95 -> 75 us vs two
-  // rounds); FS2_WGRAD_BIG_TARGET overrides for A/B runs
-  static const int tgt = getenv_int("FS2_WGRAD_BIG_TARGET", 240);
-  const int split_big = own_split(tgt, tiles_big);
+  // rounds)
+  constexpr int WGRAD_BIG_TARGET = 240;
+  const int split_big = own_split(WGRAD_BIG_TARGET, tiles_big);
   const bool slices = p.split_stride > 0 && p.split_k > 1;  // caller-chosen split, plain stores
   // persistent 256x128 kernel: short-K plain GEMMs (FS2_GEMM_NO_PK=1 restores the per-tile
   // kernels for A/B runs); 32-bit buffer offsets must cover A, B, C and the gate/residual
@@ -3092,11 +3086,10 @@ int plan_gemm(const GemmArgs& a, GemmPlan& pl) {
   // persistent 256 x 256 / 256 x 192 kernel: long-K K-major GEMMs without gate / residual
   // operands (FS2_GEMM_NO_PS=1 restores the per-tile kernels for A/B runs)
   static const bool no_ps = getenv_flag("FS2_GEMM_NO_PS");
-  // the 4-wave 128 x 128-per-wave kernel: plain K-major GEMMs with wide outputs and long K
-  // (FS2_GEMM_W4=0 in the experiments build: the 8-wave kernels, for A/B runs)
-  static const bool w4_on = getenv_int("FS2_GEMM_W4", 1) != 0;
+  // the 4-wave 128 x 128-per-wave kernel: plain K-major GEMMs with wide outputs and long K.
   // K >= 2048 and >= 160 tiles: the decoder conv2 forward (K = 1536) measured 52 vs 49 us on
   // the short-K persistent kernel, the encoder's (50 tiles of 256 x 192) 43 us
+  // (FS2_W4_MIN_K / FS2_W4_MIN_TILES force it on other shapes for tools/attn_epi_ab.sh)
   static const int w4_min_k = getenv_int("FS2_W4_MIN_K", 2048);
   static const int w4_min_tiles = getenv_int("FS2_W4_MIN_TILES", 160);
   // 256 x 256 or 256 x 192 tiles of the w4b / ps kernels: by rounds x width over the 256 CUs
@@ -3106,7 +3099,7 @@ int plan_gemm(const GemmArgs& a, GemmPlan& pl) {
   const bool w192 = (long)((t192 + 255) / 256) * 192 < (long)((t256 + 255) / 256) * 256;
   const long a_ext = ak ? (long)(p.M - 1) * p.lda + p.K : 0;
   const long b_ext = bk ? (long)(p.N - 1) * p.ldb + p.K : 0;
-  const bool w4 = w4_on && ak && bk && p.conv_mode == 0 && batch == 1 && p.split_k <= 1 &&
+  const bool w4 = ak && bk && p.conv_mode == 0 && batch == 1 && p.split_k <= 1 &&
                   !p.accumulate && !p.gate && !p.residual && !p.row_scale && !p.row_scale_post &&
                   p.K % 128 == 0 && p.K >= (p.a_kw ? 256 : max(256, w4_min_k)) &&
                   (p.a_kw || (p.N >= 384 && p.M >= 2048)) &&
@@ -3134,32 +3127,27 @@ int plan_gemm(const GemmArgs& a, GemmPlan& pl) {
     pl.kernel = K_PS6;
     return 0;
   }
-  // FS2_PS_MODES: bit 0 plain, bit 1 reflect conv (fwd), bit 2 padded-domain conv (dgrad).
-  // Default 5: in the bench step the unsplit decoder conv1 data gradient gains 0.15-0.2 ms,
-  // while the conv1 forward measured 0-0.1 ms slower than gemm256_kernel (A/B runs).
+  // Plain and padded-domain conv (dgrad) operands: in the bench step the unsplit decoder conv1
+  // data gradient gains 0.15-0.2 ms; the reflect conv (forward) measured 0-0.1 ms slower than
+  // gemm256_kernel and has no instance here.
   // Short K (256 <= K < 2048) when the tiles fill at least 200 of the 256 CUs: the decoder's
   // N = 384 / 1152 projections and FFN conv2 forward (M = 31264; tools/pk_bench.py: conv2 fwd
   // 63.8 -> 49.1 us, out_proj 29.1 -> 22.0, in_proj 65.6 -> 52.6); the encoder's 25-row-tile
-  // shapes stay on the per-tile kernels (ps 30 -> 43 us).  FS2_PS_MIN_K / FS2_PS_SHORT_TILES
-  // override for A/B runs.
-  static const int ps_modes = getenv_int("FS2_PS_MODES", 5);
-  static const int ps_min_k = getenv_int("FS2_PS_MIN_K", 256);
-  static const int ps_short_tiles = getenv_int("FS2_PS_SHORT_TILES", 200);
-  const int cm_ps = p.conv_mode == 0 ? 0
-                    : ((p.conv_mode == 1 || p.conv_mode == 4) && p.conv_dil == 1 && p.conv_c % 64 == 0
-                           ? p.conv_mode : -1);
-  const bool ps_on = cm_ps >= 0 && (ps_modes >> (cm_ps == 0 ? 0 : (cm_ps == 1 ? 1 : 2))) & 1;
+  // shapes stay on the per-tile kernels (ps 30 -> 43 us).
+  constexpr int PS_MIN_K = 256, PS_SHORT_TILES = 200;
+  const bool ps_conv4 = p.conv_mode == 4 && p.conv_dil == 1 && p.conv_c % 64 == 0;
+  const bool ps_on = p.conv_mode == 0 || ps_conv4;
   // a gate / residual operand (plain A only) takes the 256 x 192 instance (its register budget;
   // a 256 x 128 one, free of the spills of this one, measured slower: decoder gated dgrad
-  // 105-110 -> 120-122 us, step 18.05-18.11 -> 18.23-18.25 ms, tools/r04_eo.sh)
+  // 105-110 -> 120-122 us, step 18.05-18.11 -> 18.23-18.25 ms)
   const bool ps_op = p.gate || p.residual;
   const bool ps_w192 = ps_op || w192;
   const int ps_nt = ps_w192 ? t192 : t256;
   // a padded-domain output (c_row_t) exists only on this kernel: it takes every such GEMM
-  const bool ps_k = p.K >= 2048 || (p.K >= max(ps_min_k, 128) && ps_nt >= ps_short_tiles) ||
+  const bool ps_k = p.K >= 2048 || (p.K >= PS_MIN_K && ps_nt >= PS_SHORT_TILES) ||
                     (p.c_row_t && p.K >= 128);
   const bool ps_go = !no_ps && ak && bk && ps_on && batch == 1 && p.split_k <= 1 && p.vec_ok &&
-      !p.accumulate && !(p.gate && p.residual) && (!ps_op || cm_ps == 0) && p.relu <= 1 && ps_k &&
+      !p.accumulate && !(p.gate && p.residual) && (!ps_op || !ps_conv4) && p.relu <= 1 && ps_k &&
       p.N >= 128 && pk_fits;
   if (p.c_row_t && !ps_go) return FS2_EINVAL;
   if (!ps_go && !big_fits) { pl.kernel = k128; return 0; }
@@ -3170,16 +3158,13 @@ int plan_gemm(const GemmArgs& a, GemmPlan& pl) {
     const int nt = q.tiles_m * q.tiles_n;
     const int cus = p.max_ctas;
     pl.grid = dim3(nt < cus ? (nt + 7) / 8 * 8 : cus);
-    const int v = cm_ps == 0 ? 0 : cm_ps == 1 ? 1 : 2;
-    pl.kernel = K_PS + (ps_w192 ? (ps_op ? 0 : 1 + v) : 4 + v);
+    pl.kernel = K_PS + (ps_op ? 0 : (ps_w192 ? 1 : 3) + ps_conv4);
     return 0;
   }
   // narrow outputs with K >= 1152 (FFN conv2 forward, QKV data gradient) measured faster
   // on the per-tile 256x128 kernel: decoder 70.5 -> 63.6 and 58.3 -> 55.6 us, encoder
-  // 33.7 -> 29.5 and 32.7 -> 29.0 (tools/gemm_bench.py, FS2_GEMM_NO_PK A/B);
-  // FS2_PK_NARROW=1 keeps them on the persistent kernel
-  static const bool pk_narrow = getenv_flag("FS2_PK_NARROW");
-  const bool pk_shape = p.K <= 768 || p.N > 512 || pk_narrow;
+  // 33.7 -> 29.5 and 32.7 -> 29.0 (tools/gemm_bench.py, FS2_GEMM_NO_PK A/B)
+  const bool pk_shape = p.K <= 768 || p.N > 512;
   const bool pk_ok = !no_pk && ak && bk && p.conv_mode == 0 && batch == 1 && p.split_k <= 1 &&
                      p.vec_ok && !p.accumulate && !(p.gate && p.residual) && p.K > 64 && pk_fits;
   // tile of the persistent short-K kernel: 256 x 128 where those tiles fill most of a round
@@ -3218,14 +3203,13 @@ int plan_gemm(const GemmArgs& a, GemmPlan& pl) {
   }
   // 256x256 phased kernel: wide outputs (< 10 % column padding; the QKV projection's
   // N = 1152 pads 11 % and measured 100 vs 85 us on the 256x128 kernel at M = 31264)
-  static const bool no256 = getenv_flag("FS2_GEMM_NO256");
   const bool wide = p.N >= 512 && tn256 * 256 * 100 <= p.N * 110;
   const int split256 = own_split(240, t256);
   // from 150 tiles: the encoder FFN conv1 forward (M = 6400, N = 1536: 150 tiles of 256^2 in
-  // one round vs 300 of 256x128 in 1.2 rounds) 122 -> 112 us; FS2_G4_MIN_TILES overrides
-  static const int g4_min = getenv_int("FS2_G4_MIN_TILES", 150);
-  const bool use256 = !no256 && wide && p.conv_mode != 2 &&
-                      ((p.vec_ok && p.split_k <= 1 && t256 * batch >= g4_min) ||
+  // one round vs 300 of 256x128 in 1.2 rounds) 122 -> 112 us
+  constexpr int G4_MIN_TILES = 150;
+  const bool use256 = wide && p.conv_mode != 2 &&
+                      ((p.vec_ok && p.split_k <= 1 && t256 * batch >= G4_MIN_TILES) ||
                        (slices && p.vec_ok && t256 * p.split_k >= 160) ||
                        (wgrad && t256 * split256 >= 160));
   if (use256) {
@@ -3233,28 +3217,24 @@ int plan_gemm(const GemmArgs& a, GemmPlan& pl) {
     q.tiles_m = tm256, q.tiles_n = tn256;
     if (wgrad) split_wgrad(split256);
     pl.grid = dim3(t256, 1, wgrad ? q.split_k : (slices ? p.split_k : gz));
-    // full-row regions (gemm256r_kernel) for K-major A and B with 64-aligned taps;
-    // FS2_G4R=0 (experiments build) keeps gemm256_kernel
-    static const bool g4r = getenv_int("FS2_G4R", 1) != 0;
+    // full-row regions (gemm256r_kernel) for K-major A and B with 64-aligned taps
     const int cm64 = conv_variant(q, 64);
-    if (ak && bk && g4r && cm64 >= 0) {
+    if (ak && bk && cm64 >= 0) {
       // register-direct epilogue (TR): bf16 output, no gate, one K split, 8-column granules
-      static const bool g4tr = getenv_int("FS2_G4R_TR", 1) != 0;
-      const bool tr = g4tr && q.vec_ok && !q.c_fp32 && !q.gate && q.split_k <= 1 &&
+      const bool tr = q.vec_ok && !q.c_fp32 && !q.gate && q.split_k <= 1 &&
                       q.nvalid % 8 == 0 && q.ldc % 8 == 0 && (!q.residual || q.ldr % 8 == 0) &&
                       (q.relu <= 1) && !q.accumulate;
       pl.kernel = K_256R + (tr && cm64 <= 1 ? cm64 : 2 + (cm64 == 0 ? 0 : cm64 == 1 ? 1 : cm64 == 4 ? 2 : 3));
     } else {
-      pl.kernel = K_256 + tile_variant(ak, bk, conv_variant(q, 32), q.conv_mode);
+      pl.kernel = K_256 + tile_variant(ak, bk, conv_variant(q, 32), q.conv_mode) - 1;
     }
     return 0;
   }
   // 256x128 tiles down to 60 of them (M = 6400 encoder / predictor GEMMs: 75 tiles beat the
-  // 150 tiles of the 128x128 kernel, e.g. predictor conv fwd 45 -> 31 us); FS2_GEMM_BIG_MIN
-  // overrides for A/B runs
-  static const int big_min = getenv_int("FS2_GEMM_BIG_MIN", 60);
-  const bool use_big = !no_big && p.conv_mode != 2 &&
-                       ((p.vec_ok && p.split_k <= 1 && tiles_big * batch >= big_min) ||
+  // 150 tiles of the 128x128 kernel, e.g. predictor conv fwd 45 -> 31 us)
+  constexpr int BIG_MIN_TILES = 60;
+  const bool use_big = p.conv_mode != 2 &&
+                       ((p.vec_ok && p.split_k <= 1 && tiles_big * batch >= BIG_MIN_TILES) ||
                         (slices && p.vec_ok && tiles_big * p.split_k >= 160) ||
                         (wgrad && tiles_big * split_big >= 160));
   if (!use_big) { pl.kernel = k128; return 0; }

@@ -93,7 +93,7 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(LnFwdP p) {
 // block's 4R), every row's x / r / post-add loaded before the first row is reduced.  One row
 // per wave kept ~1.5 KB in flight per wave -- 48 KB per CU at full occupancy -- and ran the
 // decoder LayerNorm (96 MB) at 3.6 TB/s.  Per-row arithmetic, dropout indices and rounding
-// points are those of ln_fwd_vec_kernel<bf16, 1> (outputs bit-identical).
+// points are those of ln_fwd_vec_kernel (outputs bit-identical).
 template <int R, bool DPP>
 __global__ void __launch_bounds__(256) ln_fwd_rows_kernel(LnFwdP p) {
   constexpr int V = 8;
@@ -179,22 +179,10 @@ __global__ void __launch_bounds__(256) ln_fwd_rows_kernel(LnFwdP p) {
   }
 }
 
-// the bf16 rows kernels' row sums through DPP (wave_sum_dpp; FS2_LN_DPP=0: __shfl_xor)
-int ln_dpp() {
-  static const int r = fs2_exp_int("FS2_LN_DPP", 1);
-  return r;
-}
-// rows per wave of the bf16 LayerNorm forward (FS2_LN_FWD_ROWS: 1 = ln_fwd_vec_kernel)
-int ln_fwd_rows() {
-  static const int r = fs2_exp_int("FS2_LN_FWD_ROWS", 2);
-  return r;
-}
-
 // tanh for the bf16 backward's (1 - t^2) gate: exp-based, absolute error ~1e-7 (the gate's
 // error is 2|t| times that, far below the bf16 gradient it scales); tanhf's branchy
 // polynomial costs ~3x the instructions.  The forward keeps tanhf (its result is the layer's
-// output), and so do the fp32 kernels.  do_tanh == 2 (FS2_LN_TANH_EXACT, experiments build)
-// keeps tanhf in the bf16 backward too.
+// output), and so do the fp32 kernels.  do_tanh == 2 keeps tanhf in the bf16 backward too.
 __device__ __forceinline__ float tanh_gate(float x) {
   return 1.f - 2.f * __builtin_amdgcn_rcpf(__expf(2.f * x) + 1.f);
 }
@@ -510,10 +498,10 @@ __global__ void __launch_bounds__(256) ln_bwd_vec_kernel(LnBwdP p, float* part, 
 }
 
 // bf16, D <= 512 (one 16-byte chunk per lane): the same per-row arithmetic and the same
-// per-wave accumulation order as ln_bwd_vec_kernel<bf16, 1> (so identical results), but each
+// per-wave accumulation order as ln_bwd_vec_kernel (so identical results), but each
 // wave loads R rows (r, r+4, ..., r+4(R-1)) before computing any of them.  The one-row loop
 // keeps ~1.5 KB per wave in flight and ran at 1-2 TB/s (latency bound: 15 waves per CU).  The
-// tanh-gated case (PostNet) uses R = 2 (ln_tanh_rows).
+// tanh-gated case (PostNet) uses R = 2.
 template <int R, bool TANH, bool DPP>
 __global__ void __launch_bounds__(256) ln_bwd_rows_kernel(LnBwdP p, float* part, int npart,
                                                           int kind0) {
@@ -668,17 +656,12 @@ __global__ void __launch_bounds__(SL * 16) reduce_parts_kernel(const float* part
 // 16 row-slices (256 threads): a block that fits beside the side stream's GEMM blocks on a
 // busy CU, each thread walking 4x the rows of the 1024-thread form, whose blocks waited for a
 // whole free CU (21-27 us per call in the step against 4 standalone).  Step 17.25 -> 17.14 ms
-// (3 x 3 interleaved; 64 threads: 17.36).  FS2_RP_SL=64 (experiments build): the 1024-thread form.
+// (3 x 3 interleaved; 64 threads: 17.36).
 void launch_reduce_parts(hipStream_t st, const float* part, int nb, int D, int npart, float* o0,
                          float* o1, float* o2, int accumulate) {
-  static const int sl = fs2_exp_int("FS2_RP_SL", 16);
   const dim3 g((npart * D + 15) / 16);
-  if (sl == 16)
-    hipLaunchKernelGGL(reduce_parts_kernel<16>, g, dim3(256), 0, st, part, nb, D, npart, o0, o1,
-                       o2, accumulate);
-  else
-    hipLaunchKernelGGL(reduce_parts_kernel<64>, g, dim3(1024), 0, st, part, nb, D, npart, o0, o1,
-                       o2, accumulate);
+  hipLaunchKernelGGL(reduce_parts_kernel<16>, g, dim3(256), 0, st, part, nb, D, npart, o0, o1,
+                     o2, accumulate);
 }
 
 // column sums, 16-B loads: thread = (row sub-lane, column chunk of VEC)
@@ -870,27 +853,9 @@ __global__ void __launch_bounds__(256) sum_slices_kernel(const float* ws, int ns
 // rows per LayerNorm-backward block (4 waves at 3 waves per SIMD): enough that the grid's
 // waves fit one round of the chip's 3 x 1024 wave slots (the decoder's M = 31264: 41 rows, 763
 // blocks -- 32 rows left a second round of 836 waves: 41.6 -> 38.8 us standalone, step 17.20 ->
-// 17.13 ms, tools/r06_probe.sh), at least 16 (M = 6400: 16.9 us; 20.0 with 8)
-// FS2_LN_RPB forces
-int ln_rpb(int M) {
-  static const int r = fs2_exp_int("FS2_LN_RPB", 0);
-  if (r) return std::max(4, r);
-  return std::max(16, (4 * M + 3071) / 3072);
-}
+// 17.13 ms), at least 16 (M = 6400: 16.9 us; 20.0 with 8)
+int ln_rpb(int M) { return std::max(16, (4 * M + 3071) / 3072); }
 int ln_blocks(int M) { return min(8192, max(1, (M + ln_rpb(M) - 1) / ln_rpb(M))); }
-// rows in flight per wave in the bf16 LayerNorm backward (FS2_LN_ROWS=1 selects the one-row
-// kernel for A/B runs)
-// the tanh-gated bf16 LayerNorm backward (PostNet, D = 512) through the R = 2 rows kernel:
-// 43.2 us vs 48.7 for the one-row kernel with the same exp-based gate, 57.1 with tanhf
-// (tools/r06_ln_tanh.sh, M = 31264); FS2_LN_TANH_ROWS=0 selects the one-row kernel
-int ln_tanh_rows() {
-  static const int r = fs2_exp_int("FS2_LN_TANH_ROWS", 1);
-  return r;
-}
-int ln_rows_r() {
-  static const int r = fs2_exp_int("FS2_LN_ROWS", 4);
-  return r;
-}
 // ---- token-major -> channel-major padded images for the K-major weight gradient (conv_mode 6)
 //
 // The FFN conv1 weight gradient dW[o][j][c] = sum_{b,t} dH[b,t,o] * X[b, reflect(t+j-P), c]
@@ -1119,16 +1084,13 @@ extern "C" int fs2_ln_fwd(const void* x, int64_t ldx, const void* r, int64_t ldr
                    (!s_out || a16(s_out)) && (!post_add || (a16(post_add) && ldp % V == 0));
   if (dtype == FS2_BF16) {
     if (!vec) hipLaunchKernelGGL(ln_fwd_kernel<bf16>, grid, dim3(256), 0, s, p);
-    else if (nch == 1 && ln_fwd_rows() == 2 && a16(gamma) && a16(beta)) {
+    else if (nch == 1) {
+      // two rows per wave, row sums through DPP: 27.1 -> 25.4 us (four rows 29.6, DESIGN.md
+      // section 6.3), then 26.3 -> 24.4 us against __shfl_xor sums (section 6.9)
       p.img = (char*)img;
       img_done = true;
-      hipLaunchKernelGGL((ln_dpp() ? ln_fwd_rows_kernel<2, true> : ln_fwd_rows_kernel<2, false>), dim3((M + 7) / 8), dim3(256), 0, s, p);
-    } else if (nch == 1 && ln_fwd_rows() == 4 && a16(gamma) && a16(beta)) {
-      p.img = (char*)img;
-      img_done = true;
-      hipLaunchKernelGGL((ln_dpp() ? ln_fwd_rows_kernel<4, true> : ln_fwd_rows_kernel<4, false>), dim3((M + 15) / 16), dim3(256), 0, s, p);
+      hipLaunchKernelGGL((ln_fwd_rows_kernel<2, true>), dim3((M + 7) / 8), dim3(256), 0, s, p);
     }
-    else if (nch == 1) hipLaunchKernelGGL((ln_fwd_vec_kernel<bf16, 1>), grid, dim3(256), 0, s, p);
     else if (nch == 2) hipLaunchKernelGGL((ln_fwd_vec_kernel<bf16, 2>), grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((ln_fwd_vec_kernel<bf16, 4>), grid, dim3(256), 0, s, p);
   } else if (dtype == FS2_F32) {
@@ -1168,8 +1130,6 @@ extern "C" int fs2_ln_bwd(const void* dy, int64_t lddy, const void* s, int64_t l
            salt_o, row_mask, relu_gate_in, (char*)ds, ldds, (char*)dr, p_r, salt_r, pg, pb, M,
            D, seed, rpb, pcl, (long)npart * D};
   hipStream_t st = (hipStream_t)stream;
-  static const int tanh_exact = fs2_exp_int("FS2_LN_TANH_EXACT", 0);
-  if (tanh_exact && do_tanh) p.do_tanh = 2;
   const int V = dtype == FS2_BF16 ? 8 : 4;
   const int nch = (D / V + 63) / 64;
   const bool vec = (D % V) == 0 && nch <= 4 && a16(dy) && (lddy % V) == 0 && a16(s) &&
@@ -1179,10 +1139,11 @@ extern "C" int fs2_ln_bwd(const void* dy, int64_t lddy, const void* s, int64_t l
   const int kind0 = dgamma ? 0 : 2;
   if (dtype == FS2_BF16) {
     if (!vec) hipLaunchKernelGGL(ln_bwd_kernel<bf16>, dim3(nb), dim3(256), 0, st, p);
-    else if (nch == 1 && do_tanh && ln_tanh_rows()) hipLaunchKernelGGL((ln_dpp() ? ln_bwd_rows_kernel<2, true, true> : ln_bwd_rows_kernel<2, true, false>), dim3(nb), dim3(256), 0, st, p, part, npart, kind0);
-    else if (nch == 1 && ln_rows_r() == 4 && !do_tanh) hipLaunchKernelGGL((ln_dpp() ? ln_bwd_rows_kernel<4, false, true> : ln_bwd_rows_kernel<4, false, false>), dim3(nb), dim3(256), 0, st, p, part, npart, kind0);
-    else if (nch == 1 && ln_rows_r() == 2 && !do_tanh) hipLaunchKernelGGL((ln_dpp() ? ln_bwd_rows_kernel<2, false, true> : ln_bwd_rows_kernel<2, false, false>), dim3(nb), dim3(256), 0, st, p, part, npart, kind0);
-    else if (nch == 1) hipLaunchKernelGGL((ln_bwd_vec_kernel<bf16, 1>), dim3(nb), dim3(256), 0, st, p, part, npart, kind0);
+    // D <= 512: 4 rows per wave in flight; the tanh-gated case (PostNet) 2: 43.2 us vs 48.7 for
+    // the one-row kernel with the same exp-based gate, 57.1 with tanhf (M = 31264, DESIGN.md
+    // section 6.9)
+    else if (nch == 1 && do_tanh) hipLaunchKernelGGL((ln_bwd_rows_kernel<2, true, true>), dim3(nb), dim3(256), 0, st, p, part, npart, kind0);
+    else if (nch == 1) hipLaunchKernelGGL((ln_bwd_rows_kernel<4, false, true>), dim3(nb), dim3(256), 0, st, p, part, npart, kind0);
     else if (nch == 2) hipLaunchKernelGGL((ln_bwd_vec_kernel<bf16, 2>), dim3(nb), dim3(256), 0, st, p, part, npart, kind0);
     else hipLaunchKernelGGL((ln_bwd_vec_kernel<bf16, 4>), dim3(nb), dim3(256), 0, st, p, part, npart, kind0);
   } else if (dtype == FS2_F32) {
@@ -1194,10 +1155,7 @@ extern "C" int fs2_ln_bwd(const void* dy, int64_t lddy, const void* s, int64_t l
     return FS2_EINVAL;
   }
   FS2_CHECK_LAUNCH();
-  // FS2_LN_NORED=1 (experiments build, timing probe only -- the parameter gradients are then
-  // left unreduced): what the reduce_parts launches cost the step
-  static const int nored = fs2_exp_int("FS2_LN_NORED", 0);
-  if (npart && !nored) {
+  if (npart) {
     float* o0 = dgamma ? dgamma : dcol;
     float* o1 = dgamma ? dbeta : nullptr;
     float* o2 = dgamma ? dcol : nullptr;
@@ -1216,8 +1174,7 @@ extern "C" int fs2_colsum(const void* X, int64_t ldx, int M, int N, int dtype, f
   const int rpb = (M + nb - 1) / nb;
   const int V = dtype == FS2_BF16 ? 8 : 4;
   const bool vec = (N % V) == 0 && N / V <= 256 && a16(X) && (ldx % V) == 0;
-  static const int slab = fs2_exp_int("FS2_COLSUM_SLAB", 1);
-  if (vec && slab && N / V >= 32) {
+  if (vec && N / V >= 32) {
     const dim3 g(nb, (N / V + 63) / 64);
     if (dtype == FS2_BF16)
       hipLaunchKernelGGL((colsum_slab_kernel<bf16, 8>), g, dim3(256), 0, st, (const bf16*)X, (long)ldx, M, N, rpb, workspace);
@@ -1267,8 +1224,7 @@ extern "C" int fs2_conv_fold(const float* Xpad, int nsplit, int64_t split_stride
     return FS2_EINVAL;
   const dim3 g((unsigned)((n / 4 + 255) / 256)), b(256);
   hipStream_t s = (hipStream_t)stream;
-  static const bool no8 = fs2_exp_int("FS2_FOLD8", 1) == 0;
-  const bool v8 = !no8 && dtype == FS2_BF16 && C % 8 == 0 && a16(out) && ldo % 8 == 0 &&
+  const bool v8 = dtype == FS2_BF16 && C % 8 == 0 && a16(out) && ldo % 8 == 0 &&
                   (!residual || (a16(residual) && ldr % 8 == 0)) && a16(Xpad) &&
                   (nsplit == 1 || split_stride % 4 == 0) && n / 8 < (1L << 31);
   if (v8) {

@@ -34,9 +34,6 @@ class _Salt:
         return self.n
 
 
-_NO_FLASH = N.exp_flag("FS2_NO_FLASH")
-
-
 def dgrad_split(Mp, C, K, dt, n_cu=256, max_split=8):
     """K split for the shift-conv data gradient, chosen for wave quantisation over the 256 CUs
     (one 256x128 tile per CU at a time): the decoder's 372 tiles fill 1.45 rounds (73 %), two
@@ -45,7 +42,7 @@ def dgrad_split(Mp, C, K, dt, n_cu=256, max_split=8):
     extra plane."""
     if dt != 1:
         return 1
-    if not _NO_PS and _PS_MODES & 4 and K >= 2048 and C >= 128 and C % 4 == 0:
+    if K >= 2048 and C >= 128 and C % 4 == 0:
         # the persistent 256 x 192 / 256 x 256 kernel (gemm_ps_kernel) takes an unsplit data
         # gradient when its tiles fill most of one round (the decoder: 124 x 2 = 248 tiles)
         w = 192 if C % 256 and -(-C // 192) * 192 < -(-C // 256) * 256 else 256
@@ -63,34 +60,20 @@ def dgrad_split(Mp, C, K, dt, n_cu=256, max_split=8):
     return best
 
 
-_NO_SLICES = N.exp_flag("FS2_NO_WGRAD_SLICES")
-_NO_PS = N.exp_flag("FS2_GEMM_NO_PS")
-_PS_MODES = N.exp_int("FS2_PS_MODES", 5)
 # large weight gradients (the FFN conv1 weights, 5.3 M floats) as split-K planes + fixed-order
 # sum instead of split-K fp32 atomics: decoder 428 -> 420 us, encoder 128 -> 119 us, and the
-# result no longer depends on atomic ordering.  FS2_NO_WGRAD_BIG_SLICES=1 restores the atomics.
-_BIG_SLICES = not N.exp_flag("FS2_NO_WGRAD_BIG_SLICES")
-_SLICE_TARGET = N.exp_int("FS2_WGRAD_SLICE_TARGET", 240)
+# result no longer depends on atomic ordering.  (tile, slice) units they aim for:
+_SLICE_TARGET = 240
 # CU budget of the small weight gradients' split-K on the side stream: sliced ones fill
-# _WG_SLICE_CU CUs, the atomic ones _WG_ATOMIC_UNITS (tile, split) units (experiments build)
-_WG_SLICE_CU = N.exp_int("FS2_WG_SLICE_CU", 256)
-_WG_ATOMIC_UNITS = N.exp_int("FS2_WG_ATOMIC_UNITS", 512)
-# conv weight gradients with both operands K-major (channel-major padded images, conv_mode 6):
-# FS2_KM_WGRAD=0 restores the MN-major implicit-conv GEMM for A/B runs
-_KM_WGRAD = N.exp_int("FS2_KM_WGRAD", 1)
-# decoder FFN conv1 data gradient over the zero-padded dY image (engine._pad_dgrad)
-_PAD_DGRAD = N.exp_int("FS2_PAD_DGRAD", 1)
-# FFN conv1 forward over a reflect-padded X image (engine._pad_fwd)
-_PAD_FWD = N.exp_int("FS2_PAD_FWD", 2)
+# _WG_SLICE_CU CUs, the atomic ones _WG_ATOMIC_UNITS (tile, split) units
+_WG_SLICE_CU = 256
+_WG_ATOMIC_UNITS = 512
 # decoder FFN conv1 data gradient in the tap-inner K order (engine._tap_inner): off -- 11 %
 # faster standalone and 190 instead of 995 MB read, but the step measured 0.03-0.08 ms slower
 # with it in three same-box A/Bs (17.18 vs 17.13 ms on the final tree); the FFN conv1 forward in
 # that order (engine._tap_inner_fwd): off -- 316-318 vs 314 us for the decoder's in the step,
 # step 17.42 vs 17.37 ms (experiments library, 2 x 2 interleaved)
 _TAP_INNER = N.exp_int("FS2_TAP_INNER", 0)
-# the FFN conv1 forward's padded image written by the LayerNorm before it (FS2_LN_IMG=0,
-# experiments build: a separate fs2_pad_rows pass)
-_LN_IMG = N.exp_int("FS2_LN_IMG", 1)
 _TAP_INNER_FWD = N.exp_int("FS2_TAP_INNER_FWD", 0)
 # serial mode for per-call-site timing (bench.py --detail runs with the experiments library)
 _NO_SIDE = N.exp_flag("FS2_NO_SIDE_STREAM")
@@ -98,32 +81,17 @@ _NO_AUX = N.exp_flag("FS2_NO_AUX_STREAM")
 # persistent-GEMM grid budget of the weight-gradient side stream (fs2_gemm_desc.max_ctas, passed
 # with every weight-gradient GEMM enqueued there): the CUs it leaves free take the main stream's LayerNorm / reduction / short GEMM launches, which
 # otherwise queue behind side-stream blocks that hold a whole CU's registers.  Same-box sweep
-# (tools/r04_side.sh, 2 x 7 interleaved bench runs): 256 -> 18.23-18.29 ms, 176-240 ->
-# 18.01-18.13, 160 -> 18.87; 208 kept.  FS2_SIDE_CTAS overrides in the experiments build.
-_SIDE_CTAS = N.exp_int("FS2_SIDE_CTAS", 208)
-# AdamW of the decoder / mel-linear / PostNet parameters on the aux stream during the encoder
-# backward (FusedTrainer.step, one process); FS2_ADAM_OVERLAP=0 (experiments build): one launch
-_ADAM_OVERLAP = N.exp_int("FS2_ADAM_OVERLAP", 1)
-# the energy predictor's forward and backward on the aux stream (FS2_AUX_ENERGY=0: on the main
-# stream, its backward fused into the residual epilogue, for A/B runs)
-_AUX_ENERGY = N.exp_int("FS2_AUX_ENERGY", 1)
-# the pitch / energy embedding and speaker-embedding weight gradients on the side stream
-# (FS2_SIDE_SMALL=0: on the main stream, for A/B runs)
-_SIDE_SMALL = N.exp_int("FS2_SIDE_SMALL", 1)
-# decoder backward: skip the padded query rows whose gradients are exact zeros (engine
-# skip_grad_tail; experiments build, for A/B runs: FS2_GRAD_TAIL=0 turns it off, 1 bounds the
-# attention backward only, 3 (default) also compacts the K-major weight gradients)
-_GRAD_TAIL = N.exp_int("FS2_GRAD_TAIL", 3)
+# (DESIGN.md section 6.7, 2 x 7 interleaved bench runs): 256 -> 18.23-18.29 ms, 176-240 ->
+# 18.01-18.13, 160 -> 18.87; 208 kept.
+_SIDE_CTAS = 208
 
 
 def ps_plain_ok(M, lda, N, ldb, out_rows, ldc, out_bytes):
     """fs2_gemm can take a padded-domain GEMM (c_row output remap) only on its persistent
-    kernel: plain operands enabled (FS2_GEMM_NO_PS / FS2_PS_MODES bit 0 in the experiments
-    build) and every operand within the kernel's 32-bit buffer offsets -- otherwise the engine
+    kernel, with every operand within the kernel's 32-bit buffer offsets -- otherwise the engine
     keeps the implicit-conv path instead of handing fs2_gemm a call it refuses."""
     lim = 0x7fffffff
-    return (not _NO_PS and bool(_PS_MODES & 1) and M * lda * 2 < lim and N * ldb * 2 < lim and
-            out_rows * ldc * out_bytes < lim)
+    return M * lda * 2 < lim and N * ldb * 2 < lim and out_rows * ldc * out_bytes < lim
 
 
 def eff_split(K, ns, bk):
@@ -141,7 +109,7 @@ def wgrad_slices(O, Ncols, ldc, K, dt, n_cu=256):
     """Split-K slice count for a weight gradient with a small output: enough 256x128 tiles x
     slices to fill the 256 CUs once, each slice >= 8 K-tiles; slices are fp32 planes summed in
     a fixed order instead of tens of fp32 atomics landing on every output element.  Applied
-    where it measured faster (bench.py --detail, FS2_NO_WGRAD_SLICES=1 for the A/B): outputs of
+    where it measured faster (bench.py --detail): outputs of
     >= 256 rows and <= 256 K elements (out-projection 62 -> 55 us, PostNet conv_pre 73 -> 57 us),
     or <= 600 K elements over encoder-length K (conv2 58 -> 42 us, out-projection 47 -> 31 us).
     1 = the atomic split-K path (decoder conv2 91 vs 144 us, PostNet 150 vs 231 us)."""
@@ -209,7 +177,7 @@ class FS2Engine:
         # that bound and skips them (same bits).  skip_grad_tail = False turns the skipping off;
         # check_grad_tail (tests, with the skipping off) asserts the zero tail at every site
         # that would receive the bound and lists the sites in grad_tail_checked.
-        self.skip_grad_tail = bool(_GRAD_TAIL)
+        self.skip_grad_tail = True
         self.check_grad_tail = False
         self.grad_tail_checked = []
 
@@ -283,8 +251,8 @@ class FS2Engine:
     # ------------------------------------------------------------------ helpers
     def use_flash(self, T, dh):
         """fused attention kernels on the bf16 path (fp32 parity mode keeps the materialised
-        softmax); FS2_NO_FLASH=1 forces the materialised path for A/B runs."""
-        return self.dt == 1 and not _NO_FLASH and ops.attn_supported(T, dh, self.dt)
+        softmax)."""
+        return self.dt == 1 and ops.attn_supported(T, dh, self.dt)
 
     def ws(self, n):
         """scratch buffer of the CURRENT stream (the weight-gradient side stream has its own)"""
@@ -580,14 +548,11 @@ class FS2Engine:
         O, C, KW = self._wspecs[wname]
         # both stacks: over the image the decoder's conv1 is a plain GEMM for the 4-wave kernel
         # (gemm_w4b_kernel), step 17.54 -> 17.35 ms on one box (tools/step_ab.sh, 3 rounds);
-        # on the 8-wave implicit conv it had measured no faster.  FS2_PAD_FWD=1 (experiments
-        # build): encoder only.
-        if _PAD_FWD == 1 and not wname.startswith("encoder."):
-            return False
+        # on the 8-wave implicit conv it had measured no faster.
         P = (KW - 1) // 2
         if self._tap_inner_fwd(wname):   # the 4-wave kernel: 32-bit offsets to 2.8 M rows
             return P < T
-        return (self.dt == 1 and _PAD_FWD and KW > 1 and C % 64 == 0 and P < T and
+        return (self.dt == 1 and KW > 1 and C % 64 == 0 and P < T and
                 self.w[wname][0].shape[1] == KW * C and
                 ps_plain_ok((M // T) * (T + 2 * P), C, O, KW * C, M, O, 2))
 
@@ -605,10 +570,8 @@ class FS2Engine:
         weight image's taps reversed the shift conv is a plain K-major GEMM whose A rows
         overlap, A(m, k) = image[m * O + k] (tools/dgrad_probe.py, B = 32: decoder 417 -> 339
         us, encoder 83 -> 76) -- no per-K-tile tap offsets or row bounds in the loader."""
-        if self.dt != 1 or not _PAD_DGRAD or ".pos_ffn.0." not in wname:
+        if self.dt != 1 or ".pos_ffn.0." not in wname:
             return False
-        if _PAD_DGRAD == 2 and not wname.startswith("decoder."):
-            return False     # A/B: decoder only
         O, C, KW = self._wspecs[wname]
         return KW > 1 and self._km_ok(O, C, KW, KW, None)
 
@@ -628,9 +591,7 @@ class FS2Engine:
         built with w_okc bit 3), both stacks: the image's rows are fetched about once instead of
         once per tap.  Needs the padded path on every batch (_pad_fwd's conditions other than
         P < T, which the reference's reflect padding requires anyway)."""
-        if not (_TAP_INNER_FWD and self.dt == 1 and _PAD_FWD and ".pos_ffn.0." in wname):
-            return False
-        if _PAD_FWD == 1 and not wname.startswith("encoder."):
+        if not (_TAP_INNER_FWD and self.dt == 1 and ".pos_ffn.0." in wname):
             return False
         O, C, KW = self._wspecs[wname]
         return KW > 1 and C % 64 == 0 and (KW * C) % 128 == 0 and \
@@ -715,8 +676,6 @@ class FS2Engine:
         dY rows t >= grad_end[b] are exact zeros (the K-major path then skips them)"""
         grad_end = self._tail_bound(wname, dY, M // T, T, grad_end,
                                     T + self._wspecs[wname][2] - 1 if dy_img is not None else None)
-        if not _GRAD_TAIL & 2:
-            grad_end = None
         h = self._side_enter(dY, X, dy_img, grad_end)
         tag = self._dtag("wgrad", wname, T)
         if tag:
@@ -737,7 +696,7 @@ class FS2Engine:
         + both transposes vs the MN-major implicit-conv GEMM: decoder conv1 464 -> 372 us,
         encoder conv1 115 -> 110, PostNet 218 / 237 / 221 -> 125 / 98 / 75; the k = 3
         predictor convs lose (58 -> 67: the transposes cost more than the GEMM saves)."""
-        return (self.dt == 1 and _KM_WGRAD and KW >= 5 and n_cols is None and
+        return (self.dt == 1 and KW >= 5 and n_cols is None and
                 C % 8 == 0 and O % 8 == 0 and (KW - 1) // 2 < T)
 
     def _km_image(self, key, C, ld):
@@ -851,8 +810,8 @@ class FS2Engine:
             split = max(1, min(-(-_WG_ATOMIC_UNITS // tiles), K // (_BK[self.dt] * 4)))
         conv = (3, T, KW, C) if KW > 1 else None
         ldc = C * KW
-        ns = wgrad_slices(O, Ncols, ldc, K, self.dt, _WG_SLICE_CU) if not _NO_SLICES else 1
-        if ns == 1 and _BIG_SLICES and self.dt == 1 and Ncols == ldc and O * ldc > 600_000:
+        ns = wgrad_slices(O, Ncols, ldc, K, self.dt, _WG_SLICE_CU)
+        if ns == 1 and self.dt == 1 and Ncols == ldc and O * ldc > 600_000:
             tiles = -(-O // 256) * -(-Ncols // 256)
             ns = max(1, min(-(-_SLICE_TARGET // tiles), (K // 64) // 8))
         ns = eff_split(K, ns, _BK[self.dt])
@@ -936,9 +895,7 @@ class FS2Engine:
         img = self._fwd_image(B * (T + 2 * P1), 2 * P1, D) if self._pad_fwd(w1, M, T) else None
         ops.ln_fwd(X, D, P[prefix + "norm1.norm.weight"], P[prefix + "norm1.norm.bias"], 1e-6, X1, D,
                    mean1, rstd1, M, D, dt=self.dt, seed=seed, r=Ao, ldr=D, p_r=p_drop, salt_r=s_r1,
-                   s_out=s1, img=img if _LN_IMG else None, img_t=T, img_p=P1)
-        if img is not None and not _LN_IMG:
-            ops.pad_rows(X1, D, B, T, D, P1, 1, 2 * P1, img, D, dt=self.dt)
+                   s_out=s1, img=img, img_t=T, img_p=P1)
         del Ao
         Hc = self.empty(M, F)
         X1in = X1 if img is None else (img,)
@@ -1353,8 +1310,8 @@ class FS2Engine:
         ops.mask_rows(Z2m, D, keep_p, Mp, D, dt=self.dt)
         # with the energy target given, the energy predictor's output too only reaches the loss:
         # it joins the duration / pitch chain on the aux stream
-        aux_e = (self._aux_fork(Z2m, keep_p) if (aux_h is not None and energy is not None
-                                                 and _AUX_ENERGY) else None)
+        aux_e = (self._aux_fork(Z2m, keep_p) if (aux_h is not None and energy is not None)
+                 else None)
         pe_, ectx = self._pred_fwd(Z2m, keep_p, B, Tp, "energyPred", energy_rate, pv, seed, salt)
         if aux_e is not None:
             self._aux_exit(aux_e)
@@ -1441,7 +1398,7 @@ class FS2Engine:
                 self.on_grads_ready(tag, self.grad_streams())
                 if (self.dp_late is not None and self.adam_split is not None
                         and not self._adam_late_done and self._aux is not None
-                        and self._side is not None and _ADAM_OVERLAP and self.dp_late[0]()):
+                        and self._side is not None and self.dp_late[0]()):
                     self._adam_launch_late(self.dp_late[1])
         self._offs = {}
         d_mel = d_mel.reshape(Mm, NM).to(self.adt).contiguous()
@@ -1456,9 +1413,8 @@ class FS2Engine:
             aux_h = self._aux_fork(d_pitch, d_dur, d_energy, keep_p)
             dZpd = self._pred_pair_bwd(d_dur, ctx["dctx"], d_pitch, ctx["pctx"], keep_p, B, Tp,
                                        ctx["p_var"], seed)
-            if _AUX_ENERGY:
-                dZe = self._pred_bwd(d_energy, ctx["ectx"], keep_p, B, Tp, "energyPred",
-                                     ctx["p_var"], seed)
+            dZe = self._pred_bwd(d_energy, ctx["ectx"], keep_p, B, Tp, "energyPred",
+                                 ctx["p_var"], seed)
             self._aux_exit(aux_h)
         # mel receives the loss gradient and the PostNet residual (model.py:431)
         d_mel_total = d_mel.clone()
@@ -1492,7 +1448,7 @@ class FS2Engine:
         ops.lr_scatter(dX, ctx["cum"], keep_m, B, Tp, Tm, D, dZ3, dt=self.dt)
         def wg_side(fn, *tensors):
             # a weight-gradient-only pass on the side stream; its inputs stay unmodified after
-            h = self._side_enter(*tensors) if _SIDE_SMALL else None
+            h = self._side_enter(*tensors)
             fn()
             self._side_exit(h)
         kwe = c.energy_pred_kernel_size
@@ -1525,7 +1481,7 @@ class FS2Engine:
                                      ctx["p_var"], seed, residual=dZ2, post_mask=True)
         notify("variance")
         if (self.adam_split is not None and self._aux is not None and self._side is not None
-                and self.on_grads_ready is None and _ADAM_OVERLAP
+                and self.on_grads_ready is None
                 and not torch.cuda.is_current_stream_capturing()):
             self._adam_launch_late()
         # concat projection (Z = proj(cat) * keep) -- dZ is already masked

@@ -1,6 +1,5 @@
 """fs2_colsum (bias gradients) standalone at the step's shapes, bf16: us per call (colsum
-kernel + reduce_parts) and GB/s of the matrix read.  FS2_COLSUM_SLAB=0 on the experiments
-library: the sub-row kernel for every width."""
+kernel + reduce_parts) and GB/s of the matrix read."""
 import os
 import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
