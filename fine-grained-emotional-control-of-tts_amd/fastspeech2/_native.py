@@ -167,6 +167,13 @@ SIGNATURES = {
     "fs2_rank_pool": (I, [P, P, P, I, I, I, P, P, P]),
     "fs2_rank_loss_fwd": (I, [P, P, P, P, P, P, P, P, I, I, Fl, Fl, P, P]),
     "fs2_bucket_means": (I, [P, P, P, P, P, I, I, I, P, P]),
+    "fs2_gelu_dropout_fwd": (I, [P, I64, I, P, I64, P, I64, I, I, Fl, U32, U32, I, P]),
+    "fs2_gelu_dropout_bwd": (I, [P, I64, P, I64, P, I64, I, I, Fl, U32, U32, I, P]),
+    "fs2_intensity_head_bwd": (I, [P, P, I64, P, P, I, P, P, I, I, I, I, P, I64, P, P, P, P, I,
+                                   P]),
+    "fs2_intensity_head_bwd_workspace_floats": (I64, [I, I, I, I]),
+    "fs2_rank_pool_bwd": (I, [P, P, P, P, P, P, I, I, I, P, P, P]),
+    "fs2_rank_loss_fwd_bwd": (I, [P, P, P, P, P, P, P, P, I, I, Fl, Fl, P, P, P, P, P, P]),
     "fs2_collate_phonemes": (I, [P, P, P, P, I, I, P, P, P, P]),
     "fs2_collate_frames": (I, [P, P, P, P, P, I, I, I, P, P, P, P, P, P]),
     "fs2_vocoder_input": (I, [P, I, I, I, I, P, I, I, P]),

@@ -115,8 +115,8 @@ class RankModel(nn.Module):
     """rank_model/model.py:115-166 with the reference's attribute names, so its checkpoints load
     (``rank_model.load_state_dict(...)``, train.py:218-221).  ``.intensity_extractor`` is what
     the FastSpeech2 train path uses; ``forward`` runs in eval mode only (validation losses and
-    the prototype bank, ``fastspeech2.rank``).  Rank-model training is out of scope (DESIGN.md
-    section 7)."""
+    the prototype bank, ``fastspeech2.rank``).  Training is the subclass
+    ``fastspeech2.rank_train.TrainableRankModel``."""
 
     def __init__(self, n_mels, n_heads, n_emotions, n_encoder_layers, hidden_dim, kernel_size,
                  dropout, act_dtype=torch.float32, **kwargs):
@@ -267,23 +267,8 @@ class ExtractorEngine:
         return X0, B, T
 
     def stage_mixup(self, emo_X, neu_X, lambdas):
-        """rank_model/model.py:148-153: emo_X, neu_X fp32 (B,T,C) and lambdas fp32 (2,B) -> the
-        GEMM rows of the 2B mixed sequences (lam_i's B first, then lam_j's).  Returns
-        (X0, 2B, T)."""
-        C = self.x.n_mels + 2
-        emo_X = emo_X.to(device=self.dev, dtype=torch.float32).contiguous()
-        neu_X = neu_X.to(device=self.dev, dtype=torch.float32).contiguous()
-        B, T, Cx = emo_X.shape
-        if Cx != C or neu_X.shape != emo_X.shape:
-            raise RuntimeError(f"rank-model inputs must both be (B, T, n_mels + 2 = {C}), got "
-                               f"{tuple(emo_X.shape)} and {tuple(neu_X.shape)}")
-        lambdas = lambdas.to(device=self.dev, dtype=torch.float32).contiguous()
-        if lambdas.shape != (2, B):
-            raise RuntimeError(f"lambdas must be (2, {B}), got {tuple(lambdas.shape)}")
-        ldx = round_up(C, self.epc)
-        X0 = self.empty(2 * B * T, ldx)
-        ops.rank_mixup_input(emo_X, neu_X, lambdas, B, T, C, X0, ldx, dt=self.dt)
-        return X0, 2 * B, T
+        """rank_model/model.py:148-153: see ``stage_mixup``.  Returns (X0, 2B, T)."""
+        return stage_mixup(self.x.n_mels + 2, self.dev, self.adt, emo_X, neu_X, lambdas)
 
     def forward_staged(self, X0, B, T, length, emotions):
         """The extractor from staged input rows X0 [B*T][ldx] on: I (B, T, E) fp32."""
@@ -331,6 +316,27 @@ class ExtractorEngine:
                            P["classifier.weight"], P["classifier.bias"], B, T, D, E, I,
                            dt=self.dt)                                      # :103-107
         return I
+
+
+def stage_mixup(C, dev, adt, emo_X, neu_X, lambdas):
+    """rank_model/model.py:148-153: emo_X, neu_X fp32 (B, T, C = n_mels + 2) and lambdas fp32
+    (2, B) -> the GEMM rows of the 2B mixed sequences in the activation dtype ``adt`` on ``dev``
+    (lam_i's B first, then lam_j's).  Shared by the evaluation and the training engine.  Returns
+    (X0, 2B, T)."""
+    emo_X = emo_X.to(device=dev, dtype=torch.float32).contiguous()
+    neu_X = neu_X.to(device=dev, dtype=torch.float32).contiguous()
+    B, T, Cx = emo_X.shape
+    if Cx != C or neu_X.shape != emo_X.shape:
+        raise RuntimeError(f"rank-model inputs must both be (B, T, n_mels + 2 = {C}), got "
+                           f"{tuple(emo_X.shape)} and {tuple(neu_X.shape)}")
+    lambdas = lambdas.to(device=dev, dtype=torch.float32).contiguous()
+    if lambdas.shape != (2, B):
+        raise RuntimeError(f"lambdas must be (2, {B}), got {tuple(lambdas.shape)}")
+    dt = N.dtype_code(adt)
+    ldx = round_up(C, ops.EPC[dt])
+    X0 = torch.empty(2 * B * T, ldx, dtype=adt, device=dev)
+    ops.rank_mixup_input(emo_X, neu_X, lambdas, B, T, C, X0, ldx, dt=dt)
+    return X0, 2 * B, T
 
 
 def phoneme_average(I, durations, phon_len):

@@ -414,6 +414,43 @@ def rank_loss_fwd(lam_i, lam_j, hi, hj, ri, rj, y_emo, y_neu, B, E, alpha, beta,
          "fs2_rank_loss_fwd")
 
 
+def gelu_dropout_fwd(Z, ldz, Hc, ldh, M, N_, p, seed, salt, *, dt, z_fp32=0, Zact=None, ldza=0):
+    """``z_fp32``: Z is fp32 whatever ``dt``; ``Zact``: also Z rounded to the activation dtype."""
+    _chk(N.lib().fs2_gelu_dropout_fwd(_p(Z), ldz, z_fp32, _p(Zact), ldza, _p(Hc), ldh, M, N_, p,
+                                      seed & 0xffffffff, salt, dt, _s()), "fs2_gelu_dropout_fwd")
+
+
+def gelu_dropout_bwd(dHc, lddh, Z, ldz, dZ, lddz, M, N_, p, seed, salt, *, dt):
+    """dZ may be dHc (in place)."""
+    _chk(N.lib().fs2_gelu_dropout_bwd(_p(dHc), lddh, _p(Z), ldz, _p(dZ), lddz, M, N_, p,
+                                      seed & 0xffffffff, salt, dt, _s()), "fs2_gelu_dropout_bwd")
+
+
+def intensity_head_bwd(gI, H, ldh, emo_table, emotions, n_emotions, lengths, Wc, B, T, D, E, dH,
+                       lddh, dWc, dbc, dEmb, *, dt, ws):
+    _chk(N.lib().fs2_intensity_head_bwd(_p(gI), _p(H), ldh, _p(emo_table), _p(emotions),
+                                        n_emotions, _p(lengths), _p(Wc), B, T, D, E, _p(dH), lddh,
+                                        _p(dWc), _p(dbc), _p(dEmb), _p(ws), dt, _s()),
+         "fs2_intensity_head_bwd")
+
+
+def intensity_head_bwd_ws(B, T, D, E):
+    return N.lib().fs2_intensity_head_bwd_workspace_floats(B, T, D, E)
+
+
+def rank_pool_bwd(gI, gh, gr, h, Wp, length, B, T, E, dI, dWp):
+    """gI may be None (zeros)."""
+    _chk(N.lib().fs2_rank_pool_bwd(_p(gI), _p(gh), _p(gr), _p(h), _p(Wp), _p(length), B, T, E,
+                                   _p(dI), _p(dWp), _s()), "fs2_rank_pool_bwd")
+
+
+def rank_loss_fwd_bwd(lam_i, lam_j, hi, hj, ri, rj, y_emo, y_neu, B, E, alpha, beta, out, dhi,
+                      dhj, dri, drj):
+    _chk(N.lib().fs2_rank_loss_fwd_bwd(_p(lam_i), _p(lam_j), _p(hi), _p(hj), _p(ri), _p(rj),
+                                       _p(y_emo), _p(y_neu), B, E, alpha, beta, _p(out), _p(dhi),
+                                       _p(dhj), _p(dri), _p(drj), _s()), "fs2_rank_loss_fwd_bwd")
+
+
 def bucket_means(frames, order, cstart, utt_off, grp_off, G, K, E, out):
     _chk(N.lib().fs2_bucket_means(_p(frames), _p(order), _p(cstart), _p(utt_off), _p(grp_off),
                                   G, K, E, _p(out), _s()), "fs2_bucket_means")

@@ -8,8 +8,8 @@ Reference (emo_rank_tts/rank_model/):
   concatenated and split into ``bucket_size`` buckets, each bucket's mean a prototype.
 
 Everything runs through libfs2_hip.so (``fs2_rank_loss_fwd``, ``fs2_bucket_means``); there is
-no CPU path.  Rank-model training (backward, dropout, optimiser) is out of scope (DESIGN.md
-section 7): nothing here carries an autograd graph.
+no CPU path.  Nothing here carries an autograd graph: rank-model training (dropout, backward,
+the differentiable loss) is ``fastspeech2.rank_train``.
 """
 
 import numpy as np

@@ -463,6 +463,56 @@ int fs2_bucket_means(const float* frames, const int64_t* order, const int64_t* c
                      float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Rank-model training (rank_model/train.py:19-43): the pieces of the train-mode forward and of
+ * the backward that are not GEMMs, attention or LayerNorm.  fp32 parameter gradients, fixed
+ * summation orders, no atomics.  E <= 8; p in [0, 1).
+ * ------------------------------------------------------------------------------------------ */
+/* rank_model/model.py:42-43 (activation, dropout): Hc[m][n] = keep(m*N + n) * GELU(Z[m][n]) /
+ * (1 - p), GELU in fs2_gemm's erf form (relu = 2).  keep = the pair-hash mask of (seed, salt),
+ * indexed by m*N + n whatever the row pitches (all >= N).  Z is the conv1 output with bias and no
+ * activation: in dtype, or (z_fp32 != 0) the fp32 output of a c_fp32 GEMM, so that beside bf16
+ * activations GELU sees the unrounded value as the evaluation path's fused epilogue does.  Zact
+ * (optional): Z rounded to dtype, what fs2_gelu_dropout_bwd reads.  Hc, Zact in dtype.      */
+int fs2_gelu_dropout_fwd(const void* Z, int64_t ldz, int z_fp32, void* Zact, int64_t ldza,
+                         void* Hc, int64_t ldh, int M, int N, float p, uint32_t seed,
+                         uint32_t salt, int dtype, void* stream);
+/* its backward: dZ[m][n] = dHc[m][n] * keep(m*N + n) / (1 - p) * GELU'(Z[m][n]),
+ * GELU'(z) = (1 + erf(z / sqrt 2)) / 2 + z exp(-z^2 / 2) / sqrt(2 pi).  dZ may be dHc.       */
+int fs2_gelu_dropout_bwd(const void* dHc, int64_t lddh, const void* Z, int64_t ldz, void* dZ,
+                         int64_t lddz, int M, int N, float p, uint32_t seed, uint32_t salt,
+                         int dtype, void* stream);
+/* rank_model/model.py:103-107 backwards, from gI fp32 (B,T,E):
+ *   dH[b,t,:] = t < lengths[b] ? sum_e gI[b,t,e] Wc[e,:] : 0                       (dtype)
+ *   dWc[e,:]  = sum_{b, t < lengths[b]} gI[b,t,e] (H[b,t,:] + emo_table[emotions[b],:])
+ *   dbc[e]    = sum_{b, ALL t < T} gI[b,t,e]   (padded frames hold the bias)
+ *   dEmb[k,:] = sum_{b: emotions[b] = k} sum_{t < lengths[b]} dH[b,t,:] (before rounding);
+ *               (n_emotions, D), rows of emotions no sequence carries are exact zeros
+ * Outputs are overwritten.  workspace >= fs2_intensity_head_bwd_workspace_floats floats.    */
+int fs2_intensity_head_bwd(const float* gI, const void* H, int64_t ldh, const float* emo_table,
+                           const int64_t* emotions, int n_emotions, const int64_t* lengths,
+                           const float* Wc, int B, int T, int D, int E, void* dH, int64_t lddh,
+                           float* dWc, float* dbc, float* dEmb, float* workspace, int dtype,
+                           void* stream);
+int64_t fs2_intensity_head_bwd_workspace_floats(int B, int T, int D, int E);
+/* rank_model/model.py:160-164 backwards: dI[b,t,e] = gI[b,t,e] + (gh[b,e] + gr[b] Wp[e]) /
+ * float(length[b]) for ALL t < T (gI may be NULL: zeros); dWp[e] = sum_b gr[b] h[b,e] in
+ * ascending b.  fp32; dI and gI 16-byte aligned.                                            */
+int fs2_rank_pool_bwd(const float* gI, const float* gh, const float* gr, const float* h,
+                      const float* Wp, const int64_t* length, int B, int T, int E, float* dI,
+                      float* dWp, void* stream);
+/* rank_model/loss.py:36-55: out[0..2] as fs2_rank_loss_fwd, and the gradients of out[0]:
+ * dhi, dhj (B,E), dri, drj (B,).  F.cross_entropy is the batch mean and the per-sample lambdas
+ * multiply that scalar, so dhi[b] = alpha/B (mean(lam_i) (softmax(hi[b]) - onehot(y_emo[b])) +
+ * (1 - mean(lam_i)) (softmax(hi[b]) - onehot(y_neu[b]))); dri = -beta/B (t / (p + 1e-8) -
+ * (1 - t) / (1 - p + 1e-8)) p (1 - p), p = sigmoid(ri - rj), t = (lam_i - lam_j + 1) / 2,
+ * drj = -dri; fp32 in the reference's order (a saturated p gives exactly 0).  One block.     */
+int fs2_rank_loss_fwd_bwd(const float* lam_i, const float* lam_j, const float* hi,
+                          const float* hj, const float* ri, const float* rj,
+                          const int64_t* y_emo, const int64_t* y_neu, int B, int E, float alpha,
+                          float beta, float* out, float* dhi, float* dhj, float* dri, float* drj,
+                          void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * GPU collate: TextMelCollateWithAlignment (fastspeech2/dataset.py:62-133) over
  * one packed upload.  Item u's phonemes / durations are [offsets[u], offsets[u+1]) of the
  * packed int64 arrays; its mel is (n_mels, T_u) channel-major at frame_offsets[u] * n_mels,
