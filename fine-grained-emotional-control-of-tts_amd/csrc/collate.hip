@@ -12,6 +12,12 @@
 //                         contiguous), pitch / energy (B, Tm), and
 //                         rank_X (B, n_mels + 2, Tm) = cat(mel, pitch, energy) (:94,116-117)
 // HBM-bound byte movement: 4 B x (2 n_mels + 4) per valid frame + the zero padding.
+//
+// The rank model's pair collate (rank_model/dataset.py:71-115) over a device-resident store:
+//   rank_collate_kernel   per 64-frame tile of one row of one output: the (C, T_u) channel-major
+//                         item is read along t, transposed in LDS, and the tile's contiguous
+//                         frames x C span of emo_X / neu_X (B, T, C) is written along c; frames
+//                         past min(emo_len, neu_len) are zeros.  One launch for both outputs.
 #include "fs2_common.h"
 
 namespace {
@@ -63,6 +69,35 @@ __global__ void __launch_bounds__(256) collate_frames_kernel(
   if (blockIdx.x == 0 && threadIdx.x == 0) out_len[b] = T;
 }
 
+constexpr int RC_MAX = 130;   // n_mels + 2, n_mels <= 128
+
+// grid (tiles of T, B, 2): z = 0 the emotional item -> emo_X, z = 1 the neutral one -> neu_X.
+// Item bases and pitches are arbitrary (4-byte alignment only), so loads and stores are dwords;
+// a wave reads 64 consecutive frames of one channel and writes 64 consecutive floats of the span.
+__global__ void __launch_bounds__(256) rank_collate_kernel(
+    const float* store, const int64_t* emo_off, const int64_t* emo_len, const int64_t* neu_off,
+    const int64_t* neu_len, int T, int C, float* emo_X, float* neu_X, int64_t* length) {
+  __shared__ float tile[CT][RC_MAX + 1];   // [frame][channel]; odd pitch: conflict-free columns
+  const int b = blockIdx.y, t0 = blockIdx.x * CT, neu = blockIdx.z;
+  const long le = emo_len[b] > 0 ? emo_len[b] : 0, ln = neu_len[b] > 0 ? neu_len[b] : 0;
+  const long L = min(min(le, ln), (long)T);                 // dataset.py:93 (and the clamp to T)
+  const long pitch = neu ? ln : le;
+  const float* src = store + (neu ? neu_off[b] : emo_off[b]);
+  float* dst = (neu ? neu_X : emo_X) + ((long)b * T + t0) * C;
+  const int nf = min(CT, T - t0);                            // frames of this tile
+  const int nv = (int)max(0L, min((long)nf, L - t0));        // ... of which valid
+  for (int i = threadIdx.x; i < C * CT; i += blockDim.x) {
+    const int c = i / CT, tl = i - c * CT;
+    if (tl < nv) tile[tl][c] = src[(long)c * pitch + t0 + tl];
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nf * C; i += blockDim.x) {
+    const int tl = i / C, c = i - tl * C;
+    dst[i] = tl < nv ? tile[tl][c] : 0.f;
+  }
+  if (blockIdx.x == 0 && neu == 0 && threadIdx.x == 0) length[b] = L;
+}
+
 inline unsigned nblk(long n, int bs = 256) { return (unsigned)((n + bs - 1) / bs); }
 
 }  // namespace
@@ -94,6 +129,22 @@ extern "C" int fs2_collate_frames(const int32_t* order, const int64_t* frame_off
   hipLaunchKernelGGL(collate_frames_kernel, dim3((Tm + CT - 1) / CT, B), dim3(256), 0,
                      (hipStream_t)stream, order, frame_offsets, mel, pitch, energy, B, Tm,
                      n_mels, mel_padded, pitch_padded, energy_padded, rank_x, output_lengths);
+  FS2_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int fs2_rank_collate(const float* store, const int64_t* emo_off,
+                                const int64_t* emo_len, const int64_t* neu_off,
+                                const int64_t* neu_len, int B, int T, int C, float* emo_X,
+                                float* neu_X, int64_t* length, void* stream) {
+  if (B < 0 || T < 0) return FS2_EINVAL;
+  if ((long)B * T == 0) return 0;
+  if (!store || !emo_off || !emo_len || !neu_off || !neu_len || !emo_X || !neu_X || !length ||
+      C < 3 || C > RC_MAX || B > 65535)
+    return FS2_EINVAL;
+  hipLaunchKernelGGL(rank_collate_kernel, dim3((T + CT - 1) / CT, B, 2), dim3(256), 0,
+                     (hipStream_t)stream, store, emo_off, emo_len, neu_off, neu_len, T, C, emo_X,
+                     neu_X, length);
   FS2_CHECK_LAUNCH();
   return 0;
 }

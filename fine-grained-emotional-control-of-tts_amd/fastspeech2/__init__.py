@@ -6,6 +6,10 @@ Orca0917/fine-grained-emotional-control-of-tts ``emo_rank_tts/fastspeech2``).
     from fastspeech2.train import train_step, FusedTrainer
     from fastspeech2.optim import FusedAdamW
 
+The rank model's data path (``emo_rank_tts/rank_model/dataset.py``):
+
+    from fastspeech2 import FineGrainedDataset, RankGpuCollate, RankDeviceStore
+
 Compute runs only through libfs2_hip.so (include/fs2_hip.h); see DESIGN.md.
 """
 
@@ -14,6 +18,17 @@ import os
 import yaml
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+
+_RANK_DATASET = ("FineGrainedDataset", "RankGpuCollate", "RankDeviceStore")
+__all__ = ["load_config", *_RANK_DATASET]
+
+
+def __getattr__(name):
+    # resolved on first use, so that importing the package alone does not import torch
+    if name in _RANK_DATASET:
+        from . import rank_dataset
+        return getattr(rank_dataset, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def load_config(path=None):

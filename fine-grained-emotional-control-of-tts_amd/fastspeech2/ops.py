@@ -469,6 +469,12 @@ def collate_frames(order, frame_offsets, mel, pitch, energy, B, Tm, n_mels, mel_
                                     _p(rank_x), _p(out_len), _s()), "fs2_collate_frames")
 
 
+def rank_collate(store, emo_off, emo_len, neu_off, neu_len, B, T, C, emo_X, neu_X, length):
+    _chk(N.lib().fs2_rank_collate(_p(store), _p(emo_off), _p(emo_len), _p(neu_off), _p(neu_len),
+                                  B, T, C, _p(emo_X), _p(neu_X), _p(length), _s()),
+         "fs2_rank_collate")
+
+
 def weight_prep_table(entries):
     """Device table of fs2_wprep_desc for fs2_weight_prep_batched.  entries: list of
     (W, O, C, KW, w_okc, Wf, ldf, Wb, ldb); returns (table tensor, n, total_tiles).  The tensors

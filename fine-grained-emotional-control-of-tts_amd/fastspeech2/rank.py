@@ -150,7 +150,8 @@ def bucketize(model, batches, n_speakers, n_emotions, bucket_size):
     """rank_model/inference.py:62-118: the intensity prototype bank of a trained ``RankModel``.
 
     ``batches`` is an iterable of the rank collate's dicts (``emo_X``, ``neu_X`` (B, T,
-    n_mels+2), ``speakers``, ``emotions``, ``length``); ``model`` is on the HIP device and is
+    n_mels+2), ``speakers``, ``emotions``, ``length``), as
+    ``fastspeech2.rank_dataset.RankDeviceStore.batches(8)`` yields them; ``model`` is on the HIP device and is
     run in eval mode with ``lambdas = ones`` (the unmixed emotional input).  Returns the
     (n_speakers, n_emotions, bucket_size, n_emotions) fp32 numpy array; ``np.save`` it and pass
     the path (or the array) to ``fastspeech2.inference.get_intensity_rep``.

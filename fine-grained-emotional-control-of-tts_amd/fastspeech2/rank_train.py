@@ -511,7 +511,7 @@ class RankTrainLoss(nn.Module):
 def rank_train_step(model, criterion, optim, batch):
     """The body of rank_model/train.py:28-43 for one batch: ``batch`` is the rank collate's dict
     (``emo_X``, ``neu_X`` (B, T, n_mels+2), ``emotions``, ``length``; optionally ``lambdas``
-    (2, B) instead of the Beta(1, 1) draw).  Returns ``(loss, L_mixup, L_rank)`` as detached 0-d
+    (2, B) instead of the Beta(1, 1) draw), as ``fastspeech2.rank_dataset`` makes it.  Returns ``(loss, L_mixup, L_rank)`` as detached 0-d
     device tensors: nothing here waits for the device, the caller's ``.item()`` does."""
     dev = next(model.parameters()).device
     emo_X, neu_X = batch["emo_X"].to(dev), batch["neu_X"].to(dev)

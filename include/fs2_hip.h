@@ -530,6 +530,22 @@ int fs2_collate_frames(const int32_t* order, const int64_t* frame_offsets, const
                        float* rank_x, int64_t* output_lengths, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Rank-model pair collate (rank_model/dataset.py:71-115) from a device-resident store.  Row b's
+ * emotional item is (C, emo_len[b]) channel-major fp32 at store + emo_off[b] (row pitch
+ * emo_len[b], offsets in floats, 4-byte alignment only), its neutral item likewise; two rows may
+ * name the same item.  length[b] = min(emo_len[b], neu_len[b], T) (a negative length counts as
+ * 0; :93), emo_X[b,t,c] = emo_item[c,t] for t < length[b] and 0 for length[b] <= t < T, neu_X
+ * the same (:96-107: truncate the pair to the shorter, zero-pad to T, permute(0,2,1), here
+ * contiguous (B, T, C)).  T is the caller's: the collate's max over ALL untruncated lengths of
+ * the batch (:76-77), which may exceed every length[b].  One launch writes both outputs and
+ * length; no workspace, no atomics.  Returns 0 without a launch when B*T == 0; FS2_EINVAL for a
+ * null pointer, B < 0, T < 0, B > 65535, C < 3 or C > 130 (n_mels 1..128).
+ * ------------------------------------------------------------------------------------------ */
+int fs2_rank_collate(const float* store, const int64_t* emo_off, const int64_t* emo_len,
+                     const int64_t* neu_off, const int64_t* neu_len, int B, int T, int C,
+                     float* emo_X, float* neu_X, int64_t* length, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * HiFi-GAN generator forward (speechbrain HIFIGAN.decode_batch,
  * fastspeech2/inference.py:60-63,85).  Convs on fs2_gemm (conv_mode 1 + conv_dil, transposed
  * convs as 3-tap polyphase conv_mode 5, act 3 / 4 epilogues, residual epilogue).
