@@ -13,16 +13,17 @@ Activation storage dtype is fp32 (parity mode) or bf16 (throughput mode); parame
 gradients, LayerNorm statistics and losses are fp32 in both.
 """
 
-import math
+import contextlib
 import re
 
 import torch
 
 from . import _native as N
 from . import ops
+from .attention import attention_bwd, attention_fwd, use_flash
 from .ops import round_up
 
-_BK = {N.F32: 32, N.BF16: 64}
+BK = {N.F32: 32, N.BF16: 64}
 
 
 class _Salt:
@@ -248,11 +249,21 @@ class FS2Engine:
         if self.timer is not None:
             self.timer.stop(tag)
 
+    @contextlib.contextmanager
+    def _timed(self, kind, T):
+        """the detailed timer's tag around the attention block's fused kernel launch"""
+        tag = self._dtag(kind, "", T)
+        if tag:
+            self._tic(tag)
+        try:
+            yield
+        finally:
+            if tag:
+                self._toc(tag)
+
     # ------------------------------------------------------------------ helpers
     def use_flash(self, T, dh):
-        """fused attention kernels on the bf16 path (fp32 parity mode keeps the materialised
-        softmax)."""
-        return self.dt == 1 and ops.attn_supported(T, dh, self.dt)
+        return use_flash(T, dh, self.dt)
 
     def ws(self, n):
         """scratch buffer of the CURRENT stream (the weight-gradient side stream has its own)"""
@@ -791,7 +802,7 @@ class FS2Engine:
             # then the valid columns added into the gradient -- the unpadded GEMM's odd row
             # pitch forced the scalar atomic epilogue (92 -> ~35 us, tools/wgrad1x1_bench.py)
             K = round_up(M, self.epc)
-            ns = eff_split(K, wgrad_slices(O, n_cols, n_cols, K, self.dt), _BK[self.dt])
+            ns = eff_split(K, wgrad_slices(O, n_cols, n_cols, K, self.dt), BK[self.dt])
             ns = max(ns, 2)
             stride = O * n_cols
             ws = self.ws((ns + 1) * stride)
@@ -807,14 +818,14 @@ class FS2Engine:
         tiles = -(-O // 128) * -(-Ncols // 128)
         split = 1
         if tiles < 256:
-            split = max(1, min(-(-_WG_ATOMIC_UNITS // tiles), K // (_BK[self.dt] * 4)))
+            split = max(1, min(-(-_WG_ATOMIC_UNITS // tiles), K // (BK[self.dt] * 4)))
         conv = (3, T, KW, C) if KW > 1 else None
         ldc = C * KW
         ns = wgrad_slices(O, Ncols, ldc, K, self.dt, _WG_SLICE_CU)
         if ns == 1 and self.dt == 1 and Ncols == ldc and O * ldc > 600_000:
             tiles = -(-O // 256) * -(-Ncols // 256)
             ns = max(1, min(-(-_SLICE_TARGET // tiles), (K // 64) // 8))
-        ns = eff_split(K, ns, _BK[self.dt])
+        ns = eff_split(K, ns, BK[self.dt])
         if ns > 1:
             # small outputs: split-K slices into fp32 planes, summed in a fixed order -- instead
             # of tens of fp32 atomics landing on every output element
@@ -842,42 +853,18 @@ class FS2Engine:
     # ------------------------------------------------------------------ FFT block
     def _fft_fwd(self, X, B, T, key_pad, prefix, H, p_drop, seed, salt):
         D = self.cfg.enc_d_model
-        dh = D // H
         M = B * T
         P = self.params
         ctx = {"X": X}
         QKV = self.empty(M, 3 * D)
         self._fwd(X, D, M, T, prefix + "self_att.att.in_proj_weight", QKV, 3 * D,
                   bias=P[prefix + "self_att.att.in_proj_bias"])
-        ldt = round_up(T, 8)
         Att = self.empty(M, D)
-        if self.use_flash(T, dh):
-            # fused attention: no (B*H, T, T) tensors; lse kept for the backward
-            lse = torch.empty(B * H, T, dtype=torch.float32, device=self.dev)
-            s_att = salt()
-            tag = self._dtag("attn_fwd", "", T)
-            if tag:
-                self._tic(tag)
-            ops.attn_fwd(QKV, 3 * D, key_pad, B, H, T, dh, 1.0 / math.sqrt(dh), p_drop, seed,
-                         s_att, Att, D, lse, dt=self.dt)
-            if tag:
-                self._toc(tag)
-            Pm = Pd = None
-            ctx.update(lse=lse, key_pad=key_pad)
-        else:
-            S = torch.empty(B * H, T, ldt, dtype=torch.float32, device=self.dev)
-            ops.gemm(T, T, dh, QKV, 3 * D, QKV[:, D:], 3 * D, S, ldt, dt=self.dt, c_fp32=1,
-                     batch=B * H, batch_div=H,
-                     strides=(T * 3 * D, dh, T * 3 * D, dh, H * T * ldt, T * ldt, 0, 0))
-            Pm = self.empty(B * H, T, ldt)
-            Pd = self.empty(B * H, T, ldt) if p_drop > 0 else Pm
-            s_att = salt()
-            ops.softmax_fwd(S, key_pad, B, H, T, T, ldt, 1.0 / math.sqrt(dh), p_drop, seed, s_att,
-                            Pm, Pd if p_drop > 0 else None, dt=self.dt)
-            del S
-            ops.gemm(T, dh, ldt, Pd, ldt, QKV[:, 2 * D:], 3 * D, Att, D, dt=self.dt, b_kmajor=0,
-                     kvalid=T, batch=B * H, batch_div=H,
-                     strides=(H * T * ldt, T * ldt, T * 3 * D, dh, T * D, dh, 0, 0))
+        s_att = salt()
+        ctx.update(attention_fwd(QKV, key_pad, B, H, T, D, Att, dt=self.dt, dev=self.dev,
+                                 mask_mode=1, p_drop=p_drop, seed=seed, salt=s_att,
+                                 empty=self.empty, timed=self._timed("attn_fwd", T)),
+                   key_pad=key_pad)
         Ao = self.empty(M, D)
         self._fwd(Att, D, M, T, prefix + "self_att.att.out_proj.weight", Ao, D,
                   bias=P[prefix + "self_att.att.out_proj.bias"])
@@ -914,18 +901,16 @@ class FS2Engine:
         ops.ln_fwd(X1, D, P[prefix + "norm2.norm.weight"], P[prefix + "norm2.norm.bias"], 1e-6, X2, D,
                    mean2, rstd2, M, D, dt=self.dt, seed=seed, r=Y, ldr=D, p_r=p_drop, salt_r=s_r2,
                    s_out=s2)
-        ctx.update(QKV=QKV, Pm=Pm, Pd=Pd, Att=Att, X1=X1, s1=s1, mean1=mean1, rstd1=rstd1, Hc=Hc,
-                   s2=s2, mean2=mean2, rstd2=rstd2, s_att=s_att, s_r1=s_r1, s_r2=s_r2, F=F,
-                   ldt=ldt)
+        ctx.update(QKV=QKV, Att=Att, X1=X1, s1=s1, mean1=mean1, rstd1=rstd1, Hc=Hc, s2=s2,
+                   mean2=mean2, rstd2=rstd2, s_att=s_att, s_r1=s_r1, s_r2=s_r2, F=F)
         return X2, ctx
 
     def _fft_bwd(self, dX2, ctx, B, T, prefix, H, p_drop, seed, grad_end=None):
         """``grad_end``: int32 [B], the layer's gradient rows t >= grad_end[b] are exact zeros
         (the decoder over a padded batch, see __init__); None: no bound (the encoder)"""
         D = self.cfg.enc_d_model
-        dh = D // H
         M = B * T
-        F, ldt = ctx["F"], ctx["ldt"]
+        F = ctx["F"]
         P, G = self.params, self.grads
         lnws = self.ws(ops.ln_ws(M, D))
         ds2, dY = self.empty(M, D), self.empty(M, D)
@@ -972,46 +957,12 @@ class FS2Engine:
         self._wgrad(dAo, D, ctx["Att"], D, M, T, wo)
         self._dgrad(dAo, D, M, T, wo, dAtt, D)
         del dAo
-        QKV, Pm, Pd = ctx["QKV"], ctx["Pm"], ctx["Pd"]
-        if "lse" in ctx:     # fused attention backward (dQ, dK, dV in one pass each)
-            dQKV = self.empty(M, 3 * D)
-            tag = self._dtag("attn_bwd", "", T)
-            if tag:
-                self._tic(tag)
-            args = (QKV, 3 * D, ctx["key_pad"], ctx["Att"], D, dAtt, D, ctx["lse"], B, H, T, dh,
-                    1.0 / math.sqrt(dh), p_drop, seed, ctx["s_att"], dQKV, 3 * D)
-            ws = self.ws(ops.attn_ws(B, H, T))
-            qb = self._tail_bound(prefix + "attn_bwd", dAtt, B, T, grad_end)
-            ops.attn_bwd(*args, dt=self.dt, ws=ws, q_bound=qb)
-            if tag:
-                self._toc(tag)
-            return self._qkv_bwd(dQKV, ctx, M, T, D, prefix, ds1)
-        # ---- attention backward over the materialised probabilities
-        dPd = torch.empty(B * H, T, ldt, dtype=torch.float32, device=self.dev)
-        ops.gemm(T, T, dh, dAtt, D, QKV[:, 2 * D:], 3 * D, dPd, ldt, dt=self.dt, c_fp32=1,
-                 batch=B * H, batch_div=H,
-                 strides=(T * D, dh, T * 3 * D, dh, H * T * ldt, T * ldt, 0, 0))
         dQKV = self.empty(M, 3 * D)
-        # dV = Pd^T dO
-        ops.gemm(ldt, dh, ldt, Pd, ldt, dAtt, D, dQKV[:, 2 * D:], 3 * D, dt=self.dt, a_kmajor=0,
-                 b_kmajor=0, kvalid=T, mvalid=T, batch=B * H, batch_div=H,
-                 strides=(H * T * ldt, T * ldt, T * D, dh, T * 3 * D, dh, 0, 0))
-        dS = self.empty(B * H, T, ldt)
-        ops.softmax_bwd(dPd, Pm, B, H, T, T, ldt, 1.0 / math.sqrt(dh), p_drop, seed, ctx["s_att"], dS,
-                        dt=self.dt)
-        del dPd
-        # dQ = dS K
-        ops.gemm(T, dh, ldt, dS, ldt, QKV[:, D:], 3 * D, dQKV, 3 * D, dt=self.dt, b_kmajor=0,
-                 kvalid=T, batch=B * H, batch_div=H,
-                 strides=(H * T * ldt, T * ldt, T * 3 * D, dh, T * 3 * D, dh, 0, 0))
-        # dK = dS^T Q
-        ops.gemm(ldt, dh, ldt, dS, ldt, QKV, 3 * D, dQKV[:, D:], 3 * D, dt=self.dt, a_kmajor=0,
-                 b_kmajor=0, kvalid=T, mvalid=T, batch=B * H, batch_div=H,
-                 strides=(H * T * ldt, T * ldt, T * 3 * D, dh, T * 3 * D, dh, 0, 0))
-        del dS
-        return self._qkv_bwd(dQKV, ctx, M, T, D, prefix, ds1)
-
-    def _qkv_bwd(self, dQKV, ctx, M, T, D, prefix, ds1):
+        qb = self._tail_bound(prefix + "attn_bwd", dAtt, B, T, grad_end) if "lse" in ctx else None
+        attention_bwd(ctx["QKV"], ctx["key_pad"], ctx["Att"], dAtt, ctx, B, H, T, D, dQKV,
+                      dt=self.dt, dev=self.dev, mask_mode=1, p_drop=p_drop, seed=seed,
+                      salt=ctx["s_att"], empty=self.empty, ws=self.ws, q_bound=qb,
+                      timed=self._timed("attn_bwd", T))
         wi = prefix + "self_att.att.in_proj_weight"
         dX = self.empty(M, D)
         self._wgrad(dQKV, 3 * D, ctx["X"], D, M, T, wi)

@@ -30,13 +30,13 @@ is explicit: ``layout="BCT"`` (the collate's tensor, transposed inside the stagi
 """
 
 import copy
-import math
 
 import torch
 import torch.nn as nn
 
 from . import _native as N
 from . import ops
+from .attention import attention_fwd, use_flash
 from .ops import round_up
 
 
@@ -222,26 +222,12 @@ class ExtractorEngine:
         ops.gemm(M, O, K, X, ldx, Wf, K, out, ldo, dt=self.dt,
                  conv=(5, T, KW, C) if conv else None, **epi)
 
+    def use_flash(self, T, dh):
+        return use_flash(T, dh, self.dt)
+
     def _attention(self, QKV, key_pad, B, T, D, H, out):
-        dh = D // H
-        scale = 1.0 / math.sqrt(dh)
-        if self.dt == N.BF16 and ops.attn_supported(T, dh, self.dt):
-            lse = torch.empty(B * H, T, dtype=torch.float32, device=self.dev)
-            ops.attn_fwd(QKV, 3 * D, key_pad, B, H, T, dh, scale, 0.0, 0, 0, out, D, lse,
-                         dt=self.dt, mask_mode=0)
-            return
-        ldt = round_up(T, 8)
-        S = torch.empty(B * H, T, ldt, dtype=torch.float32, device=self.dev)
-        ops.gemm(T, T, dh, QKV, 3 * D, QKV[:, D:], 3 * D, S, ldt, dt=self.dt, c_fp32=1,
-                 batch=B * H, batch_div=H,
-                 strides=(T * 3 * D, dh, T * 3 * D, dh, H * T * ldt, T * ldt, 0, 0))
-        Pm = self.empty(B * H, T, ldt)
-        ops.softmax_fwd(S, key_pad, B, H, T, T, ldt, scale, 0.0, 0, 0, Pm, None, dt=self.dt,
-                        mask_mode=0)
-        del S
-        ops.gemm(T, dh, ldt, Pm, ldt, QKV[:, 2 * D:], 3 * D, out, D, dt=self.dt, b_kmajor=0,
-                 kvalid=T, batch=B * H, batch_div=H,
-                 strides=(H * T * ldt, T * ldt, T * 3 * D, dh, T * D, dh, 0, 0))
+        attention_fwd(QKV, key_pad, B, H, T, D, out, dt=self.dt, dev=self.dev, mask_mode=0,
+                      p_drop=0.0, seed=0, salt=0, empty=self.empty)
 
     def forward(self, x, length, emotions, layout="BTC"):
         X0, B, T = self.stage_input(x, layout)

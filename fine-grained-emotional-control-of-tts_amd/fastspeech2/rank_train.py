@@ -22,15 +22,14 @@ through them.  Every reduction has a fixed order (split-K slices summed by ``fs2
 atomics), so a step repeated from the same seed gives the same bits.
 """
 
-import math
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _native as N
 from . import ops
-from .engine import _BK, eff_split
+from .attention import attention_bwd, attention_fwd, use_flash
+from .engine import BK, eff_split
 from .intensity import RankModel, stage_mixup
 from .ops import round_up
 
@@ -91,7 +90,7 @@ class RankTrainEngine:
         return torch.empty(max(int(n), 4), dtype=torch.float32, device=self.dev)
 
     def use_flash(self, T, dh):
-        return self.dt == N.BF16 and ops.attn_supported(T, dh, self.dt)
+        return use_flash(T, dh, self.dt)
 
     # ------------------------------------------------------------------ GEMM forms
     def _fwd(self, X, ldx, M, T, wname, out, ldo, conv=False, **epi):
@@ -113,7 +112,7 @@ class RankTrainEngine:
     def _slices(self, O, ncols, K):
         """split-K slice count of a weight gradient: about one (tile, slice) unit per CU, at
         least four K-tiles per slice"""
-        bk = _BK[self.dt]
+        bk = BK[self.dt]
         tiles = -(-O // 128) * -(-ncols // 128)
         return eff_split(K, max(1, min(256 // tiles, (K // bk) // 4)), bk)
 
@@ -173,8 +172,6 @@ class RankTrainEngine:
         ext = self.x
         self.prepare()
         D, H, E = ext.hidden, ext.n_heads, ext.n_emotions
-        dh = D // H
-        scale = 1.0 / math.sqrt(dh)
         M = B * T
         P = self.p
         p_drop = float(p_drop)
@@ -193,26 +190,9 @@ class RankTrainEngine:
             self._fwd(X, D, M, T, p + "self_attn.in_proj_weight", QKV, 3 * D,
                       bias=P[p + "self_attn.in_proj_bias"])
             Att = self.empty(M, D)
-            if self.use_flash(T, dh):
-                lse = f32(B * H, T)
-                ops.attn_fwd(QKV, 3 * D, key_pad, B, H, T, dh, scale, p_drop, seed, s_att, Att, D,
-                             lse, dt=self.dt, mask_mode=0)
-                c.update(lse=lse)
-            else:
-                ldt = round_up(T, 8)
-                S = f32(B * H, T, ldt)
-                ops.gemm(T, T, dh, QKV, 3 * D, QKV[:, D:], 3 * D, S, ldt, dt=self.dt, c_fp32=1,
-                         batch=B * H, batch_div=H,
-                         strides=(T * 3 * D, dh, T * 3 * D, dh, H * T * ldt, T * ldt, 0, 0))
-                Pm = self.empty(B * H, T, ldt)
-                Pd = self.empty(B * H, T, ldt) if p_drop > 0 else Pm
-                ops.softmax_fwd(S, key_pad, B, H, T, T, ldt, scale, p_drop, seed, s_att, Pm,
-                                Pd if p_drop > 0 else None, dt=self.dt, mask_mode=0)
-                del S
-                ops.gemm(T, dh, ldt, Pd, ldt, QKV[:, 2 * D:], 3 * D, Att, D, dt=self.dt,
-                         b_kmajor=0, kvalid=T, batch=B * H, batch_div=H,
-                         strides=(H * T * ldt, T * ldt, T * 3 * D, dh, T * D, dh, 0, 0))
-                c.update(Pm=Pm, Pd=Pd, ldt=ldt)
+            c.update(attention_fwd(QKV, key_pad, B, H, T, D, Att, dt=self.dt, dev=self.dev,
+                                   mask_mode=0, p_drop=p_drop, seed=seed, salt=s_att,
+                                   empty=self.empty))
             Ao = self.empty(M, D)
             self._fwd(Att, D, M, T, p + "self_attn.out_proj.weight", Ao, D,
                       bias=P[p + "self_attn.out_proj.bias"])
@@ -257,8 +237,6 @@ class RankTrainEngine:
         fp32 gradient in the parameter's shape} for every extractor parameter."""
         ext = self.x
         D, H, E, KW = ext.hidden, ext.n_heads, ext.n_emotions, ext.kernel
-        dh = D // H
-        scale = 1.0 / math.sqrt(dh)
         B, T, p_drop, seed, P = ctx["B"], ctx["T"], ctx["p"], ctx["seed"], ctx["P"]
         # the weight images (and, in fp32, P itself) are the current parameters': a backward
         # after a parameter changed would mix them with the forward's activations
@@ -307,31 +285,9 @@ class RankTrainEngine:
             del dAo
             QKV = c["QKV"]
             dQKV = self.empty(M, 3 * D)
-            if "lse" in c:
-                ops.attn_bwd(QKV, 3 * D, ctx["key_pad"], c["Att"], D, dAtt, D, c["lse"], B, H, T,
-                             dh, scale, p_drop, seed, c["s_att"], dQKV, 3 * D, dt=self.dt,
-                             ws=self._ws(ops.attn_ws(B, H, T)), mask_mode=0)
-            else:
-                ldt, Pm, Pd = c["ldt"], c["Pm"], c["Pd"]
-                sPT = (H * T * ldt, T * ldt)
-                dPd = torch.empty(B * H, T, ldt, dtype=torch.float32, device=self.dev)
-                ops.gemm(T, T, dh, dAtt, D, QKV[:, 2 * D:], 3 * D, dPd, ldt, dt=self.dt, c_fp32=1,
-                         batch=B * H, batch_div=H,
-                         strides=(T * D, dh, T * 3 * D, dh, *sPT, 0, 0))
-                ops.gemm(ldt, dh, ldt, Pd, ldt, dAtt, D, dQKV[:, 2 * D:], 3 * D, dt=self.dt,
-                         a_kmajor=0, b_kmajor=0, kvalid=T, mvalid=T, batch=B * H, batch_div=H,
-                         strides=(*sPT, T * D, dh, T * 3 * D, dh, 0, 0))       # dV = Pd^T dO
-                dS = self.empty(B * H, T, ldt)
-                ops.softmax_bwd(dPd, Pm, B, H, T, T, ldt, scale, p_drop, seed, c["s_att"], dS,
-                                dt=self.dt)
-                del dPd
-                ops.gemm(T, dh, ldt, dS, ldt, QKV[:, D:], 3 * D, dQKV, 3 * D, dt=self.dt,
-                         b_kmajor=0, kvalid=T, batch=B * H, batch_div=H,
-                         strides=(*sPT, T * 3 * D, dh, T * 3 * D, dh, 0, 0))   # dQ = dS K
-                ops.gemm(ldt, dh, ldt, dS, ldt, QKV, 3 * D, dQKV[:, D:], 3 * D, dt=self.dt,
-                         a_kmajor=0, b_kmajor=0, kvalid=T, mvalid=T, batch=B * H, batch_div=H,
-                         strides=(*sPT, T * 3 * D, dh, T * 3 * D, dh, 0, 0))   # dK = dS^T Q
-                del dS
+            attention_bwd(c["QKV"], ctx["key_pad"], c["Att"], dAtt, c, B, H, T, D, dQKV,
+                          dt=self.dt, dev=self.dev, mask_mode=0, p_drop=p_drop, seed=seed,
+                          salt=c["s_att"], empty=self.empty, ws=self._ws)
             del dAtt
             wi = p + "self_attn.in_proj_weight"
             self._wgrad(dQKV, 3 * D, c["X"], D, M, 3 * D, D, G[wi])

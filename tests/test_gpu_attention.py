@@ -122,6 +122,25 @@ def _small_blocks(B, H, T):
     return -(-T // 128) * B * H < 256
 
 
+def _ref64(qkv, dout, pad, B, H, T, dh, p_drop, mask_mode, seed, salt):
+    """float64 attention on the given (bf16) values qkv [B*T][3D], dout [B*T][D], pad (B, T) on
+    the device: (o, lse, q, k, v, mask), o and the leaves q, k, v (B, H, T, dh) with .grad set"""
+    x = qkv.double().view(B, T, 3, H, dh)
+    q, k, v = (x[:, :, i].permute(0, 2, 1, 3).clone().requires_grad_(True) for i in range(3))
+    mask = _union_mask(pad, H, mask_mode)
+    assert bool((~mask).any(-1).all()), "every (b, h) needs a valid key"
+    s = (q @ k.transpose(-1, -2)) * (1.0 / math.sqrt(dh))
+    sm = s.masked_fill(mask, float("-inf"))
+    lse_ref = torch.logsumexp(sm.detach(), -1)
+    P = torch.softmax(sm, -1)
+    if p_drop > 0:
+        keep = _keep(seed, salt, B * H * T, T, p_drop).view(B, H, T, T).to(qkv.device)
+        P = P * keep / (1 - p_drop)
+    o = P @ v
+    o.backward(dout.double().view(B, T, H, dh).permute(0, 2, 1, 3))
+    return o.detach(), lse_ref, q, k, v, mask
+
+
 def _run_fused(cuda, parity_log, key, B, H, T, dh, p_drop, pad, mask_mode=1, ramp_k=False,
                gaps=(0, 0, 0, 0), seed=77, salt=5):
     """one fused forward + two backward calls against float64; returns (figures, float64 out)"""
@@ -143,21 +162,8 @@ def _run_fused(cuda, parity_log, key, B, H, T, dh, p_drop, pad, mask_mode=1, ram
     kp = pad.to(torch.uint8).contiguous()
     scale = 1.0 / math.sqrt(dh)
 
-    # float64 reference on the same bf16 values
-    x = qkv[:, :3 * D].double().view(B, T, 3, H, dh)
-    q, k, v = (x[:, :, i].permute(0, 2, 1, 3).clone().requires_grad_(True) for i in range(3))
-    mask = _union_mask(pad, H, mask_mode)
-    assert bool((~mask).any(-1).all()), "every (b, h) needs a valid key"
-    s = (q @ k.transpose(-1, -2)) * scale
-    sm = s.masked_fill(mask, float("-inf"))
-    lse_ref = torch.logsumexp(sm.detach(), -1)
-    P = torch.softmax(sm, -1)
-    if p_drop > 0:
-        keep = _keep(seed, salt, B * H * T, T, p_drop).view(B, H, T, T).to(cuda)
-        P = P * keep / (1 - p_drop)
-    o = P @ v
-    o.backward(dout[:, :D].double().view(B, T, H, dh).permute(0, 2, 1, 3))
-    o = o.detach()
+    o, lse_ref, q, k, v, mask = _ref64(qkv[:, :3 * D], dout[:, :D], pad, B, H, T, dh, p_drop,
+                                       mask_mode, seed, salt)
 
     out = torch.full((B * T, ldo), NAN, device=cuda, dtype=bf)
     out[:, D:] = SENTINEL
@@ -427,3 +433,54 @@ def test_fused_and_materialised_paths_agree(cuda, parity_log):
     print("fused vs materialised", err)
     _log_max(parity_log, "attn_fused_vs_materialised", {"out": err})
     assert err < 2e-2
+
+
+# ------------------------------------------------------------------ H: the engines' attention block
+@pytest.mark.parametrize("mask_mode", [0, 1])
+@pytest.mark.parametrize("p", [0.0, 0.1])
+def test_attention_block_both_paths_vs_float64(cuda, parity_log, p, mask_mode):
+    """fastspeech2.attention (what every engine calls): forward and backward once on the fused
+    path and once with it forced off, every buffer they are handed NaN-filled; out and dQKV on
+    the rows of non-padded queries against float64, the materialised Pd's zero pattern against
+    the numpy keep mask.  T = 130 crosses the 64- and 128-row tile edges and ldt = 136 != T."""
+    from fastspeech2.attention import attention_bwd, attention_fwd, use_flash
+    B, H, dh, T = 3, 2, 64, 130
+    D = H * dh
+    seed, salt = 77, 5
+    bf = torch.bfloat16
+    torch.manual_seed(130)
+    qkv = (torch.randn(B * T, 3 * D, device=cuda) * 0.5).to(bf)
+    dout = torch.randn(B * T, D, device=cuda).to(bf)
+    pad = _prefix_pad([130, 125, 65], T).to(cuda)
+    kp = pad.to(torch.uint8).contiguous()
+    o, _, q, k, v, mask = _ref64(qkv, dout, pad, B, H, T, dh, p, mask_mode, seed, salt)
+    rows = lambda t: t.permute(0, 2, 1, 3).reshape(B * T, D)
+    want = {"out": rows(o), "dq": rows(q.grad), "dk": rows(k.grad), "dv": rows(v.grad)}
+    live_q = ~pad.view(B * T)
+    assert use_flash(T, dh, 1)
+    empty = lambda *shape: torch.full(shape, NAN, device=cuda, dtype=bf)
+    kw = dict(dt=1, dev=cuda, mask_mode=mask_mode, p_drop=p, seed=seed, salt=salt, empty=empty)
+    for flash in (None, False):
+        out, dqkv = empty(B * T, D), empty(B * T, 3 * D)
+        saved = attention_fwd(qkv, kp, B, H, T, D, out, flash=flash, **kw)
+        assert ("lse" in saved) == (flash is None)
+        attention_bwd(qkv, kp, out, dout, saved, B, H, T, D, dqkv,
+                      ws=lambda n: torch.full((int(n),), NAN, device=cuda), **kw)
+        got = {"out": out, "dq": dqkv[:, :D], "dk": dqkv[:, D:2 * D], "dv": dqkv[:, 2 * D:]}
+        figs = {n: rel(got[n][live_q], want[n][live_q]) for n in got}
+        name = "attn_block_" + ("fused" if flash is None else "materialised")
+        print(name, (p, mask_mode), figs)
+        _log_max(parity_log, name, figs)
+        assert figs["out"] < TOL_OUT, figs
+        assert all(figs[n] < TOL_GRAD for n in ("dq", "dk", "dv")), figs   # a NaN fails
+        if flash is None:
+            continue
+        Pm, Pd, ldt = saved["Pm"], saved["Pd"], saved["ldt"]
+        assert ldt == 136 and Pm.shape == (B * H, T, ldt)
+        if p == 0:
+            assert Pd is Pm
+            continue
+        keep = _keep(seed, salt, B * H * T, T, p).view(B * H, T, T).to(cuda)
+        live = ~mask.view(B * H, 1, T).expand(-1, T, -1) & (Pm[..., :T] != 0)
+        assert bool(live.any())
+        assert torch.equal((Pd[..., :T] != 0)[live], keep[live])

@@ -474,15 +474,14 @@ def test_training_forward_without_dropout_is_the_eval_forward(cuda, golden, trai
     tr = m(*args, lambdas=inp["lambdas"])
     ev = m.eval()(*args, lambdas=inp["lambdas"])
     assert tr[4].requires_grad and not ev[4].requires_grad
-    tol = {"I": 1e-4, "h": 1e-4, "r": 1e-4} if dt == "fp32" else \
-        {"I": 3e-2, "h": 1.5e-3, "r": 2.8e-3}                 # test_gpu_rank.py's F32 / BF16_TOL
+    # at p = 0 the same bits, fp32 and bf16.  The two engines share the attention block
+    # (fastspeech2.attention) but not every launch: training runs conv1 into fp32 and then
+    # fs2_gelu_dropout_fwd where evaluation has the GELU epilogue, and its LayerNorms take the
+    # dropout arguments (bf16: a second call for s), so the equality also rests on those kernels
+    # agreeing at p = 0
     for name, a, b in zip(RT.NAMES, tr, ev):
-        if name.startswith("lam"):
-            assert torch.equal(a, b)
-        else:
-            e = rel(a.detach(), b)
-            print(f"train vs eval {dt} {name}: rel {e:.3e}")
-            assert e < tol[name[0]], (name, e)
+        print(f"train vs eval {dt} {name}: rel {rel(a.detach(), b):.3e}")
+        assert torch.equal(a.detach(), b), name
 
 
 def test_backward_refuses_parameters_changed_since_the_forward(cuda, golden, train_ref):
