@@ -12,7 +12,7 @@
 //
 // One wave per (z, query) row; scores fp32, probabilities stored in the activation dtype.
 // Dropout: fs2_attn_keep(dkey, row, k) (fs2_common.h; the same draw as flash.hip).
-#include "fs2_common.h"
+#include "fs2_launch.h"
 
 namespace {
 
@@ -99,15 +99,11 @@ extern "C" int fs2_softmax_fwd(const float* S, const uint8_t* key_pad, int mask_
   const long nrows = (long)B * H * Tq;
   dim3 grid((unsigned)((nrows + 3) / 4));
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FS2_BF16)
-    hipLaunchKernelGGL(softmax_fwd_kernel<bf16>, grid, dim3(256), 0, s, S, key_pad, mask_mode != 0, B, H, Tq, Tk,
-                       ldt, scale, p_drop, seed, salt, (bf16*)P, (bf16*)Pd, nrows);
-  else if (dtype == FS2_F32)
-    hipLaunchKernelGGL(softmax_fwd_kernel<float>, grid, dim3(256), 0, s, S, key_pad, mask_mode != 0, B, H, Tq, Tk,
-                       ldt, scale, p_drop, seed, salt, (float*)P, (float*)Pd, nrows);
-  else return FS2_EINVAL;
-  FS2_CHECK_LAUNCH();
-  return 0;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using U = decltype(t);
+    hipLaunchKernelGGL(softmax_fwd_kernel<U>, grid, dim3(256), 0, s, S, key_pad, mask_mode != 0, B,
+                       H, Tq, Tk, ldt, scale, p_drop, seed, salt, (U*)P, (U*)Pd, nrows);
+  });
 }
 
 extern "C" int fs2_softmax_bwd(const float* dPd, const void* P, int B, int H, int Tq, int Tk,
@@ -118,15 +114,11 @@ extern "C" int fs2_softmax_bwd(const float* dPd, const void* P, int B, int H, in
   const long nrows = (long)B * H * Tq;
   dim3 grid((unsigned)((nrows + 3) / 4));
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FS2_BF16)
-    hipLaunchKernelGGL(softmax_bwd_kernel<bf16>, grid, dim3(256), 0, s, dPd, (const bf16*)P, Tk, ldt,
-                       scale, p_drop, seed, salt, (bf16*)dS, nrows);
-  else if (dtype == FS2_F32)
-    hipLaunchKernelGGL(softmax_bwd_kernel<float>, grid, dim3(256), 0, s, dPd, (const float*)P, Tk,
-                       ldt, scale, p_drop, seed, salt, (float*)dS, nrows);
-  else return FS2_EINVAL;
-  FS2_CHECK_LAUNCH();
-  return 0;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using U = decltype(t);
+    hipLaunchKernelGGL(softmax_bwd_kernel<U>, grid, dim3(256), 0, s, dPd, (const U*)P, Tk, ldt,
+                       scale, p_drop, seed, salt, (U*)dS, nrows);
+  });
 }
 
 // this translation unit's dropout seed base (fs2_common.h)

@@ -18,7 +18,7 @@
 //                         item is read along t, transposed in LDS, and the tile's contiguous
 //                         frames x C span of emo_X / neu_X (B, T, C) is written along c; frames
 //                         past min(emo_len, neu_len) are zeros.  One launch for both outputs.
-#include "fs2_common.h"
+#include "fs2_launch.h"
 
 namespace {
 
@@ -97,8 +97,6 @@ __global__ void __launch_bounds__(256) rank_collate_kernel(
   }
   if (blockIdx.x == 0 && neu == 0 && threadIdx.x == 0) length[b] = L;
 }
-
-inline unsigned nblk(long n, int bs = 256) { return (unsigned)((n + bs - 1) / bs); }
 
 }  // namespace
 

@@ -25,18 +25,11 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "fs2_common.h"
-
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-__device__ void llvm_raw_buffer_load_lds(i32x4 rsrc, __attribute__((address_space(3))) uint32_t* lds,
-                                         int size, int voffset, int soffset, int offset,
-                                         int aux) __asm("llvm.amdgcn.raw.buffer.load.lds");
+#include "fs2_cdna.h"
+#include "fs2_launch.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr int TMAX = 2048;
 
@@ -98,9 +91,6 @@ __device__ __forceinline__ bf16x8 lds_tr_frag(const char* t, int rowbytes, int r
 // s_waitcnt vmcnt(0) in front of it -- which drained the next tile's K/V (Q/dO) prefetch in the
 // middle of every tile (profiles/r04_attention_pmc.json: SQ_WAIT_ANY 44-51 % of wave cycles).
 // The asm read is invisible to that pass; its results are retired by lds_wait<N> below.
-__device__ __forceinline__ uint32_t lds_off(const void* p) {
-  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
-}
 struct TrFrag { s16x4 lo, hi; };
 __device__ __forceinline__ void lds_tr_frag_issue(TrFrag& f, const char* t, int rowbytes, int rbase,
                                                   int m0, int lane) {
@@ -134,29 +124,6 @@ __device__ __forceinline__ void load_tile(char* t, const bf16* src, long ld, int
     if (r0 + r < nrows) v = *(const u32x4*)(src + (long)(r0 + r) * ld + c * 8);
     *(u32x4*)(t + r * DH * 2 + ((c ^ (r & 7)) << 4)) = v;
   }
-}
-
-// Buffer-resource LDS-DMA (buffer_load_dwordx4 ... lds): wave-uniform base, 32-bit lane
-// offset, lanes at BUF_OOB load zeros.
-constexpr int BUF_OOB = (int)0x80000000u;
-__device__ __forceinline__ i32x4 make_rsrc(const void* base) {
-  const uint64_t a = (uint64_t)base;
-  i32x4 r;
-  r[0] = __builtin_amdgcn_readfirstlane((int)(a & 0xffffffffu));
-  r[1] = __builtin_amdgcn_readfirstlane((int)(a >> 32));
-  r[2] = 0x7fffffff;
-  r[3] = 0x00020000;
-  return r;
-}
-__device__ __forceinline__ void blds16(i32x4 rsrc, int voff, int soff, char* lds_wave_base) {
-  llvm_raw_buffer_load_lds(rsrc, (__attribute__((address_space(3))) uint32_t*)lds_wave_base, 16,
-                           voff, soff, 0, 0);
-}
-
-// 4-byte variant: 64 lanes x 4 B land contiguously (one float per lane, e.g. a row statistic)
-__device__ __forceinline__ void blds4(i32x4 rsrc, int voff, int soff, char* lds_wave_base) {
-  llvm_raw_buffer_load_lds(rsrc, (__attribute__((address_space(3))) uint32_t*)lds_wave_base, 4,
-                           voff, soff, 0, 0);
 }
 
 // A 64-row x DH tile image (16-byte chunk c of row r stored at c ^ (r & 7)) filled by LDS-DMA:
@@ -1081,13 +1048,11 @@ void launch_bwd(const AttnP& p, hipStream_t s) {
   hipLaunchKernelGGL(attn_bwd_dkv_kernel<DH>, g1, dim3(512), 0, s, p);
 }
 
-bool a16(const void* q) { return ((uintptr_t)q & 15) == 0; }
-
 int check(int B, int H, int T, int dh, long ldq, const void* qkv, int dtype) {
   if (dtype != FS2_BF16) return FS2_EINVAL;
   if (B <= 0 || H <= 0 || T <= 0 || T > TMAX) return FS2_EINVAL;
   if (dh != 64 && dh != 128 && dh != 192 && dh != 256) return FS2_EINVAL;
-  if (!qkv || !a16(qkv) || (ldq % 8) || ldq < 3L * H * dh) return FS2_EALIGN;
+  if (!qkv || !aligned16(qkv) || (ldq % 8) || ldq < 3L * H * dh) return FS2_EALIGN;
   return 0;
 }
 
@@ -1103,7 +1068,7 @@ extern "C" int fs2_attn_fwd(const void* qkv, int64_t ldq, const uint8_t* key_pad
                             uint32_t salt, void* out, int64_t ldo, float* lse, int dtype,
                             void* stream) {
   if (int rc = check(B, H, T, dh, ldq, qkv, dtype)) return rc;
-  if (!key_pad || !out || !lse || !a16(out) || (ldo % 8)) return FS2_EINVAL;
+  if (!key_pad || !out || !lse || !aligned16(out) || (ldo % 8)) return FS2_EINVAL;
   AttnP p{};
   p.qkv = (const bf16*)qkv; p.ldq = ldq; p.kpad = key_pad; p.tiled = mask_mode != 0;
   p.out = (bf16*)out; p.ldout = ldo; p.lse = lse;
@@ -1132,7 +1097,8 @@ static int attn_bwd_impl(const void* qkv, int64_t ldq, const uint8_t* key_pad, i
                          void* stream) {
   if (int rc = check(B, H, T, dh, ldq, qkv, dtype)) return rc;
   if (!key_pad || !out || !dout || !lse || !dqkv || !workspace) return FS2_EINVAL;
-  if (!a16(out) || !a16(dout) || !a16(dqkv) || (ldo % 8) || (lddo % 8) || (lddq % 8))
+  if (!aligned16(out) || !aligned16(dout) || !aligned16(dqkv) || (ldo % 8) || (lddo % 8) ||
+      (lddq % 8))
     return FS2_EALIGN;
   AttnP p{};
   p.qkv = (const bf16*)qkv; p.ldq = ldq; p.kpad = key_pad; p.tiled = mask_mode != 0;

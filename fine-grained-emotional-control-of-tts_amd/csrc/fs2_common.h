@@ -15,15 +15,22 @@ typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
 // FS2_* A/B switches: read from the environment only in the experiments build
 // (make experiments, -DFS2_EXPERIMENTS, used by tools/); the product library compiles every
-// switch to its default.
+// switch to its default.  A variable that is unset or empty reads as the default; a flag is on
+// for anything else but "0".
 #ifdef FS2_EXPERIMENTS
 #include <cstdlib>
+#include <cstring>
 inline int fs2_exp_int(const char* name, int dflt) {
   const char* v = std::getenv(name);
   return v && v[0] ? std::atoi(v) : dflt;
 }
+inline bool fs2_exp_flag(const char* name) {
+  const char* v = std::getenv(name);
+  return v && v[0] && std::strcmp(v, "0") != 0;
+}
 #else
 constexpr int fs2_exp_int(const char*, int dflt) { return dflt; }
+constexpr bool fs2_exp_flag(const char*) { return false; }
 #endif
 
 __device__ __forceinline__ float to_f(float x) { return x; }

@@ -19,34 +19,21 @@
 // the current tile's MFMAs run; one barrier per K-tile.
 #include <type_traits>
 
-#include "fs2_common.h"
+#include "fs2_cdna.h"
+#include "fs2_launch.h"
 
 #include <cstdlib>
 #include <cstring>
-
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-__device__ void llvm_raw_buffer_load_lds(i32x4 rsrc, __attribute__((address_space(3))) uint32_t* lds,
-                                         int size, int voffset, int soffset, int offset,
-                                         int aux) __asm("llvm.amdgcn.raw.buffer.load.lds");
 
 namespace {
 
 // Measurement switches (FS2_* environment variables and the g4_flags timing bits, some of
 // which produce WRONG results on purpose) exist only in a build with -DFS2_EXPERIMENTS, the
-// one tools/ A/B runs use; the product library compiles them to their defaults.
+// one tools/ A/B runs use; the product library compiles them to their defaults
+// (fs2_exp_flag / fs2_exp_int, fs2_common.h).
 #ifdef FS2_EXPERIMENTS
-bool getenv_flag(const char* name) {
-  const char* v = std::getenv(name);
-  return v && v[0] && std::strcmp(v, "0") != 0;
-}
-int getenv_int(const char* name, int dflt) {
-  const char* v = std::getenv(name);
-  return v ? std::atoi(v) : dflt;
-}
 #define XFLAGS(p) ((p).g4_flags)
 #else
-constexpr bool getenv_flag(const char*) { return false; }
-constexpr int getenv_int(const char*, int dflt) { return dflt; }
 #define XFLAGS(p) 0
 #endif
 
@@ -253,24 +240,6 @@ __device__ __forceinline__ void glds16(const char* src, char* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((const gptr_t*)src, (lptr_t*)lds_wave_base, 16, 0, 0);
 }
 
-// Buffer-resource form of the LDS-DMA (buffer_load_dwordx4 ... lds): a wave-uniform base in
-// SGPRs, a 32-bit per-lane byte offset and a uniform SGPR offset.  Lanes with the offset
-// BUF_OOB fall outside num_records and load zeros -- no per-lane pointer selects.
-constexpr int BUF_OOB = (int)0x80000000u;
-__device__ __forceinline__ i32x4 make_rsrc(const void* base) {
-  const uint64_t a = (uint64_t)base;
-  i32x4 r;
-  r[0] = __builtin_amdgcn_readfirstlane((int)(a & 0xffffffffu));
-  r[1] = __builtin_amdgcn_readfirstlane((int)(a >> 32));
-  r[2] = 0x7fffffff;
-  r[3] = 0x00020000;
-  return r;
-}
-__device__ __forceinline__ void blds16(i32x4 rsrc, int voff, int soff, char* lds_wave_base) {
-  llvm_raw_buffer_load_lds(rsrc, (__attribute__((address_space(3))) uint32_t*)lds_wave_base, 16,
-                           voff, soff, 0, 0);
-}
-
 // K-major tile (128 rows x 128 B): 16 x 1 KiB pieces, wave w issues pieces 4w..4w+3 (8 rows each)
 __device__ __forceinline__ void glds_kmajor(char* lds, const char* base, long ld, int row0,
                                             int nrows, int k0, int kend, const GemmP& p,
@@ -340,9 +309,6 @@ __device__ __forceinline__ void glds_mnmajor(char* lds, const char* base, long l
 __device__ __forceinline__ int cs_swz(int row) { return (row & 15) << 2; }
 
 // ---- fragment readers -------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
 // bf16 16x16x32 operand, lane l: rows (mn) r0 + (l&15), k = s*32 + 8*(l>>4) + j, j = 0..7
 __device__ __forceinline__ bf16x8 frag_bf16_kmajor(const char* lds, int r0, int s, int lane) {
   const int r = r0 + (lane & 15);
@@ -358,7 +324,6 @@ __device__ __forceinline__ bf16x8 frag_bf16_mnmajor(const char* lds, int r0, int
   const char* a2 = lds + k2 * 256 + ((c ^ mn_swz<bf16>(k2)) << 4) + boff;
   const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)a1);
   const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)a2);
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
   const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   return __builtin_bit_cast(bf16x8, v);
 }
@@ -368,9 +333,6 @@ __device__ __forceinline__ bf16x8 frag_bf16_mnmajor(const char* lds, int r0, int
 // in the MN-major instances (the weight gradients) that drained the whole prefetch ring at
 // every K-tile.  The asm reads are invisible to that pass; mn_ready() after an explicit
 // lgkmcnt wait hands the registers back to the compiler.
-__device__ __forceinline__ uint32_t lds_off(const void* p) {
-  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
-}
 template <int ROWB>   // bytes per k-row of the image: 256 (128 mn) or 512 (256 mn)
 __device__ __forceinline__ bf16x8 frag_bf16_mnmajor_asm(const char* lds, int r0, int s, int lane) {
   const int li = lane & 15, g = lane >> 4, q = li >> 2, p = li & 3;
@@ -382,7 +344,6 @@ __device__ __forceinline__ bf16x8 frag_bf16_mnmajor_asm(const char* lds, int r0,
   s16x4 lo, hi;
   asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"(lds_off(a1)));
   asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(hi) : "v"(lds_off(a2)));
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
   const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   return __builtin_bit_cast(bf16x8, v);
 }
@@ -2925,8 +2886,6 @@ int tile_variant(int ak, int bk, int cm, int conv_mode) {
   return ak ? 8 : 9;
 }
 
-bool aligned16(const void* ptr) { return ((uintptr_t)ptr & 15) == 0; }
-
 // the argument checks (host): a.p or an FS2_E* code; 1 for an empty problem (nothing to run)
 int validate(const fs2_gemm_desc* d, GemmArgs& a) {
   if (!d || d->M < 0 || d->N < 0 || d->K < 0) return FS2_EINVAL;
@@ -3070,7 +3029,7 @@ int plan_gemm(const GemmArgs& a, GemmPlan& pl) {
   const bool slices = p.split_stride > 0 && p.split_k > 1;  // caller-chosen split, plain stores
   // persistent 256x128 kernel: short-K plain GEMMs (FS2_GEMM_NO_PK=1 restores the per-tile
   // kernels for A/B runs); 32-bit buffer offsets must cover A, B, C and the gate/residual
-  static const bool no_pk = getenv_flag("FS2_GEMM_NO_PK");
+  static const bool no_pk = fs2_exp_flag("FS2_GEMM_NO_PK");
   const long lim = 0x7fffffffL;
   const long crows = p.c_row_t && p.c_row_pad > 0
                          ? p.mvalid + ((long)p.mvalid / p.c_row_t + 1) * p.c_row_pad
@@ -3085,13 +3044,13 @@ int plan_gemm(const GemmArgs& a, GemmPlan& pl) {
   const bool big_fits = a_rows * p.lda * 2 < lim && b_rows * p.ldb * 2 < lim;
   // persistent 256 x 256 / 256 x 192 kernel: long-K K-major GEMMs without gate / residual
   // operands (FS2_GEMM_NO_PS=1 restores the per-tile kernels for A/B runs)
-  static const bool no_ps = getenv_flag("FS2_GEMM_NO_PS");
+  static const bool no_ps = fs2_exp_flag("FS2_GEMM_NO_PS");
   // the 4-wave 128 x 128-per-wave kernel: plain K-major GEMMs with wide outputs and long K.
   // K >= 2048 and >= 160 tiles: the decoder conv2 forward (K = 1536) measured 52 vs 49 us on
   // the short-K persistent kernel, the encoder's (50 tiles of 256 x 192) 43 us
   // (FS2_W4_MIN_K / FS2_W4_MIN_TILES force it on other shapes for tools/attn_epi_ab.sh)
-  static const int w4_min_k = getenv_int("FS2_W4_MIN_K", 2048);
-  static const int w4_min_tiles = getenv_int("FS2_W4_MIN_TILES", 160);
+  static const int w4_min_k = fs2_exp_int("FS2_W4_MIN_K", 2048);
+  static const int w4_min_tiles = fs2_exp_int("FS2_W4_MIN_TILES", 160);
   // 256 x 256 or 256 x 192 tiles of the w4b / ps kernels: by rounds x width over the 256 CUs
   // (ties to the wider tile)
   const int tm256 = (p.M + 255) / 256, tn256 = (p.N + 255) / 256, tn192 = (p.N + 191) / 192;
@@ -3112,14 +3071,14 @@ int plan_gemm(const GemmArgs& a, GemmPlan& pl) {
     q.tiles_m = tm256;
     q.tiles_n = w192 ? tn192 : tn256;
     q.a_bytes = (int)(a_ext * 2), q.b_bytes = (int)(b_ext * 2);
-    q.g4_flags = getenv_int("FS2_W4_FLAGS", 0);
+    q.g4_flags = fs2_exp_int("FS2_W4_FLAGS", 0);
     pl.grid = dim3(q.tiles_m * q.tiles_n);
     pl.kernel = K_W4B + (w192 ? 0 : 2) + (p.c_fp32 ? 0 : 1);
     return 0;
   }
   if (p.conv_mode == 6) {
     if (!p.vec_align) return FS2_EALIGN;
-    q.g4_flags = getenv_int("FS2_PS_FLAGS", 0);
+    q.g4_flags = fs2_exp_int("FS2_PS_FLAGS", 0);
     q.tiles_m = tm256, q.tiles_n = tn256;
     const int nu = q.tiles_m * q.tiles_n * max(1, p.split_k);
     if (nu > 1024) return FS2_EINVAL;   // one unit per block (gemm_ps_kernel BT)
@@ -3152,7 +3111,7 @@ int plan_gemm(const GemmArgs& a, GemmPlan& pl) {
   if (p.c_row_t && !ps_go) return FS2_EINVAL;
   if (!ps_go && !big_fits) { pl.kernel = k128; return 0; }
   if (ps_go) {
-    q.g4_flags = getenv_int("FS2_PS_FLAGS", 0);
+    q.g4_flags = fs2_exp_int("FS2_PS_FLAGS", 0);
     q.tiles_m = tm256;
     q.tiles_n = ps_w192 ? tn192 : tn256;
     const int nt = q.tiles_m * q.tiles_n;
@@ -3186,11 +3145,11 @@ int plan_gemm(const GemmArgs& a, GemmPlan& pl) {
       if (c24 < best) { pk_cfg = 24; best = c24; }
       if (c22 < best) { pk_cfg = 22; best = c22; }
     }
-    static const int force = getenv_int("FS2_PK_CFG", 0);
+    static const int force = fs2_exp_int("FS2_PK_CFG", 0);
     if (force == 44 || force == 24 || force == 22) pk_cfg = force;
   }
   if (pk_cfg) {
-    q.g4_flags = getenv_int("FS2_PK_FLAGS", 0);
+    q.g4_flags = fs2_exp_int("FS2_PK_FLAGS", 0);
     const int TM = pk_cfg == 44 ? 256 : 128, TN = pk_cfg == 22 ? 64 : 128;
     q.tiles_m = (p.M + TM - 1) / TM;
     q.tiles_n = (p.N + TN - 1) / TN;
@@ -3213,7 +3172,7 @@ int plan_gemm(const GemmArgs& a, GemmPlan& pl) {
                        (slices && p.vec_ok && t256 * p.split_k >= 160) ||
                        (wgrad && t256 * split256 >= 160));
   if (use256) {
-    q.g4_flags = getenv_int("FS2_G4_FLAGS", 0);
+    q.g4_flags = fs2_exp_int("FS2_G4_FLAGS", 0);
     q.tiles_m = tm256, q.tiles_n = tn256;
     if (wgrad) split_wgrad(split256);
     pl.grid = dim3(t256, 1, wgrad ? q.split_k : (slices ? p.split_k : gz));
@@ -3238,7 +3197,7 @@ int plan_gemm(const GemmArgs& a, GemmPlan& pl) {
                         (slices && p.vec_ok && tiles_big * p.split_k >= 160) ||
                         (wgrad && tiles_big * split_big >= 160));
   if (!use_big) { pl.kernel = k128; return 0; }
-  q.g4_flags = getenv_int("FS2_BIG_FLAGS", 0);
+  q.g4_flags = fs2_exp_int("FS2_BIG_FLAGS", 0);
   q.tiles_m = (p.M + BBM - 1) / BBM;
   if (wgrad) split_wgrad(split_big);
   pl.grid = dim3(q.tiles_m * q.tiles_n, 1, wgrad ? q.split_k : (slices ? p.split_k : gz));

@@ -15,7 +15,7 @@
 //   phon_avg_kernel         out[b][p] = sum_{t in seg(b,p)} I[b][t] / max(d[b][p], 1) for
 //                           p < phon_len[b], 0 elsewhere (train.py:33-49: repeat_interleave +
 //                           index_add_ + clamp(min=1)); one block per utterance
-#include "fs2_common.h"
+#include "fs2_launch.h"
 
 namespace {
 
@@ -94,8 +94,6 @@ __global__ void __launch_bounds__(256) phon_avg_kernel(const float* I, int Tt, i
   }
 }
 
-inline unsigned nblk(long n, int bs = 256) { return (unsigned)((n + bs - 1) / bs); }
-
 }  // namespace
 
 extern "C" int fs2_intensity_input(const float* x, int layout_bct, int B, int T, int C, void* X,
@@ -104,15 +102,11 @@ extern "C" int fs2_intensity_input(const float* x, int layout_bct, int B, int T,
   if (n == 0) return 0;
   if (!x || !X || ldx < C) return FS2_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FS2_BF16)
-    hipLaunchKernelGGL(intensity_input_kernel<bf16>, dim3(nblk(n)), dim3(256), 0, s, x,
-                       layout_bct, T, C, (bf16*)X, ldx, n);
-  else if (dtype == FS2_F32)
-    hipLaunchKernelGGL(intensity_input_kernel<float>, dim3(nblk(n)), dim3(256), 0, s, x,
-                       layout_bct, T, C, (float*)X, ldx, n);
-  else return FS2_EINVAL;
-  FS2_CHECK_LAUNCH();
-  return 0;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using U = decltype(t);
+    hipLaunchKernelGGL(intensity_input_kernel<U>, dim3(nblk(n)), dim3(256), 0, s, x, layout_bct,
+                       T, C, (U*)X, ldx, n);
+  });
 }
 
 extern "C" int fs2_intensity_head(const void* H, int64_t ldh, const float* emo_table,
@@ -125,15 +119,11 @@ extern "C" int fs2_intensity_head(const void* H, int64_t ldh, const float* emo_t
     return FS2_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const dim3 g(nblk(M, 4));
-  if (dtype == FS2_BF16)
-    hipLaunchKernelGGL(intensity_head_kernel<bf16>, g, dim3(256), 0, s, (const bf16*)H, ldh,
-                       emo_table, emotions, lengths, Wc, bc, B, T, D, E, I);
-  else if (dtype == FS2_F32)
-    hipLaunchKernelGGL(intensity_head_kernel<float>, g, dim3(256), 0, s, (const float*)H, ldh,
-                       emo_table, emotions, lengths, Wc, bc, B, T, D, E, I);
-  else return FS2_EINVAL;
-  FS2_CHECK_LAUNCH();
-  return 0;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using U = decltype(t);
+    hipLaunchKernelGGL(intensity_head_kernel<U>, g, dim3(256), 0, s, (const U*)H, ldh, emo_table,
+                       emotions, lengths, Wc, bc, B, T, D, E, I);
+  });
 }
 
 extern "C" int fs2_phoneme_average(const float* I, int T, int E, const int64_t* durations,

@@ -11,7 +11,7 @@
 //    divided by the tie count (torch amax/amin semantics).
 // All reductions are fp32 and deterministic (fixed-order block sums, no float atomics
 // except the two per-utterance SSIM normalisation sums).
-#include "fs2_common.h"
+#include "fs2_launch.h"
 
 namespace {
 
@@ -546,10 +546,8 @@ extern "C" int fs2_loss_fwd_bwd(const fs2_loss_desc* d, void* stream) {
   p.loss_out = d->loss_out; p.d_mel = d->d_mel_out; p.d_post = d->d_postnet_out;
   p.d_dur = d->d_log_dur; p.d_pitch = d->d_pitch; p.d_energy = d->d_energy;
   carve(p, d->workspace);
-  {
-    const auto al = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-    p.vec = al(p.mel_out) && al(p.post_out) && al(p.mel_tgt) && al(p.d_mel) && al(p.d_post);
-  }
+  p.vec = aligned16(p.mel_out) && aligned16(p.post_out) && aligned16(p.mel_tgt) &&
+          aligned16(p.d_mel) && aligned16(p.d_post);
   hipStream_t s = (hipStream_t)stream;
   if (d->dtype == FS2_BF16) return run_loss<bf16>(p, s);
   if (d->dtype == FS2_F32) return run_loss<float>(p, s);

@@ -10,7 +10,7 @@
 //
 // One 64-lane wave per row; statistics in fp32 with a two-pass (mean, then centred
 // variance) over the row held in registers, matching torch's LayerNorm numerics.
-#include "fs2_common.h"
+#include "fs2_launch.h"
 
 namespace {
 
@@ -1053,7 +1053,6 @@ __global__ void __launch_bounds__(256) pad_rows_kernel(const bf16* X, long ldx, 
 }
 
 int colsum_blocks(int M) { return min(512, max(1, (M + 63) / 64)); }
-bool a16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -1069,7 +1068,7 @@ extern "C" int fs2_ln_fwd(const void* x, int64_t ldx, const void* r, int64_t ldr
   if (M <= 0) return 0;
   if (D <= 0 || D > 64 * MAXJ || !x || !y || !gamma || !beta || !mean || !rstd) return FS2_EINVAL;
   if (img && (dtype != FS2_BF16 || img_t <= 0 || M % img_t || img_p < 0 || img_p >= img_t ||
-              (D % 8) || !a16(img)))
+              (D % 8) || !aligned16(img)))
     return FS2_EINVAL;
   LnFwdP p{(const char*)x, ldx, (const char*)r, ldr, p_r, salt_r, (char*)s_out, gamma, beta,
            eps, do_tanh, p_o, salt_o, row_mask, (const char*)post_add, ldp, (char*)y, ldy, mean,
@@ -1077,11 +1076,11 @@ extern "C" int fs2_ln_fwd(const void* x, int64_t ldx, const void* r, int64_t ldr
   bool img_done = false;
   dim3 grid((M + 3) / 4);
   hipStream_t s = (hipStream_t)stream;
-  const int V = dtype == FS2_BF16 ? 8 : 4;
+  const int V = vec_elems(dtype);
   const int nch = (D / V + 63) / 64;
-  const bool vec = (D % V) == 0 && nch <= 4 && a16(x) && (ldx % V) == 0 && a16(y) &&
-                   (ldy % V) == 0 && a16(gamma) && a16(beta) && (!r || (a16(r) && ldr % V == 0)) &&
-                   (!s_out || a16(s_out)) && (!post_add || (a16(post_add) && ldp % V == 0));
+  const bool vec = (D % V) == 0 && nch <= 4 && aligned16(x) && (ldx % V) == 0 && aligned16(y) &&
+                   (ldy % V) == 0 && aligned16(gamma) && aligned16(beta) && (!r || (aligned16(r) && ldr % V == 0)) &&
+                   (!s_out || aligned16(s_out)) && (!post_add || (aligned16(post_add) && ldp % V == 0));
   if (dtype == FS2_BF16) {
     if (!vec) hipLaunchKernelGGL(ln_fwd_kernel<bf16>, grid, dim3(256), 0, s, p);
     else if (nch == 1) {
@@ -1130,11 +1129,11 @@ extern "C" int fs2_ln_bwd(const void* dy, int64_t lddy, const void* s, int64_t l
            salt_o, row_mask, relu_gate_in, (char*)ds, ldds, (char*)dr, p_r, salt_r, pg, pb, M,
            D, seed, rpb, pcl, (long)npart * D};
   hipStream_t st = (hipStream_t)stream;
-  const int V = dtype == FS2_BF16 ? 8 : 4;
+  const int V = vec_elems(dtype);
   const int nch = (D / V + 63) / 64;
-  const bool vec = (D % V) == 0 && nch <= 4 && a16(dy) && (lddy % V) == 0 && a16(s) &&
-                   (lds % V) == 0 && a16(ds) && (ldds % V) == 0 && (!dr || a16(dr)) &&
-                   a16(gamma) && a16(beta);
+  const bool vec = (D % V) == 0 && nch <= 4 && aligned16(dy) && (lddy % V) == 0 && aligned16(s) &&
+                   (lds % V) == 0 && aligned16(ds) && (ldds % V) == 0 && (!dr || aligned16(dr)) &&
+                   aligned16(gamma) && aligned16(beta);
   float* part = npart ? workspace : nullptr;
   const int kind0 = dgamma ? 0 : 2;
   if (dtype == FS2_BF16) {
@@ -1172,29 +1171,28 @@ extern "C" int fs2_colsum(const void* X, int64_t ldx, int M, int N, int dtype, f
   hipStream_t st = (hipStream_t)stream;
   const int nb = colsum_blocks(M);
   const int rpb = (M + nb - 1) / nb;
-  const int V = dtype == FS2_BF16 ? 8 : 4;
-  const bool vec = (N % V) == 0 && N / V <= 256 && a16(X) && (ldx % V) == 0;
+  const int V = vec_elems(dtype);
+  const bool vec = (N % V) == 0 && N / V <= 256 && aligned16(X) && (ldx % V) == 0;
+  int rc;
   if (vec && N / V >= 32) {
     const dim3 g(nb, (N / V + 63) / 64);
-    if (dtype == FS2_BF16)
-      hipLaunchKernelGGL((colsum_slab_kernel<bf16, 8>), g, dim3(256), 0, st, (const bf16*)X, (long)ldx, M, N, rpb, workspace);
-    else if (dtype == FS2_F32)
-      hipLaunchKernelGGL((colsum_slab_kernel<float, 8>), g, dim3(256), 0, st, (const float*)X, (long)ldx, M, N, rpb, workspace);
-    else
-      return FS2_EINVAL;
-  } else if (dtype == FS2_BF16) {
-    if (vec)
-      hipLaunchKernelGGL(colsum_vec_kernel<bf16>, dim3(nb), dim3(256), 0, st, (const bf16*)X, (long)ldx, M, N, rpb, workspace);
-    else
-      hipLaunchKernelGGL(colsum_partial_kernel<bf16>, dim3((N + 255) / 256, nb), dim3(256), 0, st, (const bf16*)X, ldx, M, N, rpb, workspace);
-  } else if (dtype == FS2_F32) {
-    if (vec)
-      hipLaunchKernelGGL(colsum_vec_kernel<float>, dim3(nb), dim3(256), 0, st, (const float*)X, (long)ldx, M, N, rpb, workspace);
-    else
-      hipLaunchKernelGGL(colsum_partial_kernel<float>, dim3((N + 255) / 256, nb), dim3(256), 0, st, (const float*)X, ldx, M, N, rpb, workspace);
+    rc = dispatch_dtype(dtype, [&](auto t) {
+      using U = decltype(t);
+      hipLaunchKernelGGL((colsum_slab_kernel<U, 8>), g, dim3(256), 0, st, (const U*)X, (long)ldx,
+                         M, N, rpb, workspace);
+    });
   } else {
-    return FS2_EINVAL;
+    rc = dispatch_dtype(dtype, [&](auto t) {
+      using U = decltype(t);
+      if (vec)
+        hipLaunchKernelGGL(colsum_vec_kernel<U>, dim3(nb), dim3(256), 0, st, (const U*)X,
+                           (long)ldx, M, N, rpb, workspace);
+      else
+        hipLaunchKernelGGL(colsum_partial_kernel<U>, dim3((N + 255) / 256, nb), dim3(256), 0, st,
+                           (const U*)X, ldx, M, N, rpb, workspace);
+    });
   }
+  if (rc) return rc;
   launch_reduce_parts(st, workspace, nb, N, 1, out, nullptr, nullptr, accumulate);
   FS2_CHECK_LAUNCH();
   return 0;
@@ -1203,7 +1201,7 @@ extern "C" int fs2_colsum(const void* X, int64_t ldx, int M, int N, int dtype, f
 extern "C" int fs2_sum_slices(const float* ws, int nslices, int64_t stride, int64_t n,
                               float* out, int accumulate, void* stream) {
   if (n == 0) return 0;
-  if (!ws || !out || nslices < 1 || (n % 4) || (stride % 4) || !a16(ws) || !a16(out))
+  if (!ws || !out || nslices < 1 || (n % 4) || (stride % 4) || !aligned16(ws) || !aligned16(out))
     return FS2_EINVAL;
   const long n4 = n / 4;
   hipLaunchKernelGGL(sum_slices_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0,
@@ -1224,25 +1222,23 @@ extern "C" int fs2_conv_fold(const float* Xpad, int nsplit, int64_t split_stride
     return FS2_EINVAL;
   const dim3 g((unsigned)((n / 4 + 255) / 256)), b(256);
   hipStream_t s = (hipStream_t)stream;
-  const bool v8 = dtype == FS2_BF16 && C % 8 == 0 && a16(out) && ldo % 8 == 0 &&
-                  (!residual || (a16(residual) && ldr % 8 == 0)) && a16(Xpad) &&
+  const bool v8 = dtype == FS2_BF16 && C % 8 == 0 && aligned16(out) && ldo % 8 == 0 &&
+                  (!residual || (aligned16(residual) && ldr % 8 == 0)) && aligned16(Xpad) &&
                   (nsplit == 1 || split_stride % 4 == 0) && n / 8 < (1L << 31);
   if (v8) {
     const unsigned n8 = (unsigned)(n / 8);
     hipLaunchKernelGGL(conv_fold8_kernel, dim3((n8 + 255) / 256), b, 0, s, Xpad, nsplit,
                        (long)split_stride, T, P, C / 8, (bf16*)out, (long)ldo,
                        (const bf16*)residual, (long)ldr, row_scale, row_scale_post, n8);
-  } else if (dtype == FS2_BF16)
-    hipLaunchKernelGGL(conv_fold_kernel<bf16>, g, b, 0, s, Xpad, nsplit, (long)split_stride, T,
-                       P, C, (bf16*)out, (long)ldo, (const bf16*)residual, (long)ldr, row_scale,
+    FS2_CHECK_LAUNCH();
+    return 0;
+  }
+  return dispatch_dtype(dtype, [&](auto t) {
+    using U = decltype(t);
+    hipLaunchKernelGGL(conv_fold_kernel<U>, g, b, 0, s, Xpad, nsplit, (long)split_stride, T, P, C,
+                       (U*)out, (long)ldo, (const U*)residual, (long)ldr, row_scale,
                        row_scale_post, n);
-  else if (dtype == FS2_F32)
-    hipLaunchKernelGGL(conv_fold_kernel<float>, g, b, 0, s, Xpad, nsplit, (long)split_stride, T,
-                       P, C, (float*)out, (long)ldo, (const float*)residual, (long)ldr, row_scale,
-                       row_scale_post, n);
-  else return FS2_EINVAL;
-  FS2_CHECK_LAUNCH();
-  return 0;
+  });
 }
 
 // this translation unit's dropout seed base (fs2_common.h)
@@ -1255,7 +1251,7 @@ static int pad_transpose_impl(const void* X, int64_t ldx, int B, int T, int C, i
   if (B <= 0 || T <= 0 || C <= 0) return 0;
   if (dtype != FS2_BF16 || !X || !out || P < 0 || (reflect && P >= T)) return FS2_EINVAL;
   if ((C % 8) || (ldx % 8) || (ldo % 8) || (ncols % 8) || ncols < (long)B * (T + 2 * P) ||
-      ldo < ncols || !a16(X) || !a16(out))
+      ldo < ncols || !aligned16(X) || !aligned16(out))
     return FS2_EALIGN;
   if (colsum && (reflect || !workspace)) return FS2_EINVAL;
   if (offs && (ksplit < 1 || (ncols % (64 * ksplit)) || ncols < 128)) return FS2_EINVAL;
@@ -1315,7 +1311,7 @@ extern "C" int fs2_pad_rows(const void* X, int64_t ldx, int B, int T, int C, int
   if (B <= 0 || T <= 0 || C <= 0) return 0;
   if (dtype != FS2_BF16 || !X || !out || P < 0 || tail < 0 || (reflect && P >= T))
     return FS2_EINVAL;
-  if ((C % 8) || (ldx % 8) || (ldo % 8) || ldo < C || ldx < C || !a16(X) || !a16(out))
+  if ((C % 8) || (ldx % 8) || (ldo % 8) || ldo < C || ldx < C || !aligned16(X) || !aligned16(out))
     return FS2_EALIGN;
   const long rows = (long)B * (T + 2 * P) + tail;
   const long n8 = rows * (C / 8);

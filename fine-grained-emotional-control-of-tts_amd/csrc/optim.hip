@@ -10,7 +10,7 @@
 // weight_prep turns each torch-layout master weight W[O][C][KW] (fp32) into the two GEMM
 // operand images the MFMA kernels read K-major: Wf[O][KW*C] (forward) and Wb[C][KW*O]
 // (data gradient), cast to the activation dtype.
-#include "fs2_common.h"
+#include "fs2_launch.h"
 
 namespace {
 
@@ -349,13 +349,12 @@ extern "C" int fs2_adamw_prep(const fs2_wprep_desc* descs, int n, int total_tile
   const AdamScal a{decay_mul, one_minus_beta1, beta2, one_minus_beta2, step_size, bc2_sqrt, eps,
                    grad_scale};
   if (n > 0 && total_tiles > 0) {
-    if (dtype == FS2_BF16)
-      hipLaunchKernelGGL(adamw_prep_tiles_kernel<bf16>, dim3(total_tiles), dim3(256), 0, s, descs,
-                         n, param, grad, exp_avg, exp_avg_sq, a);
-    else
-      hipLaunchKernelGGL(adamw_prep_tiles_kernel<float>, dim3(total_tiles), dim3(256), 0, s,
-                         descs, n, param, grad, exp_avg, exp_avg_sq, a);
-    FS2_CHECK_LAUNCH();
+    if (int rc = dispatch_dtype(dtype, [&](auto t) {
+          using U = decltype(t);
+          hipLaunchKernelGGL(adamw_prep_tiles_kernel<U>, dim3(total_tiles), dim3(256), 0, s, descs,
+                             n, param, grad, exp_avg, exp_avg_sq, a);
+        }))
+      return rc;
   }
   if (n_ranges > 0 && range_blocks > 0) {
     hipLaunchKernelGGL(adamw_ranges_kernel, dim3(range_blocks), dim3(256), 0, s, ranges, n_ranges,
@@ -370,15 +369,10 @@ extern "C" int fs2_weight_prep_batched(const fs2_wprep_desc* descs, int n, int t
   if (n == 0 || total_tiles == 0) return 0;
   if (!descs || n < 0 || n > 256 || total_tiles < 0) return FS2_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FS2_BF16)
-    hipLaunchKernelGGL(weight_prep_batched_kernel<bf16>, dim3(total_tiles), dim3(256), 0, s,
-                       descs, n);
-  else if (dtype == FS2_F32)
-    hipLaunchKernelGGL(weight_prep_batched_kernel<float>, dim3(total_tiles), dim3(256), 0, s,
-                       descs, n);
-  else return FS2_EINVAL;
-  FS2_CHECK_LAUNCH();
-  return 0;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using U = decltype(t);
+    hipLaunchKernelGGL(weight_prep_batched_kernel<U>, dim3(total_tiles), dim3(256), 0, s, descs, n);
+  });
 }
 
 extern "C" int fs2_adamw(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
@@ -416,13 +410,9 @@ extern "C" int fs2_weight_prep(const float* W, int O, int C, int KW, int w_okc, 
   const long n = max((long)O * ldf, Wb ? (long)C * ldb : 0L);
   const dim3 g((unsigned)((n + 255) / 256)), b(256);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FS2_BF16)
-    hipLaunchKernelGGL(weight_prep_kernel<bf16>, g, b, 0, s, W, O, C, KW, w_okc, (bf16*)Wf, ldf,
-                       (bf16*)Wb, ldb);
-  else if (dtype == FS2_F32)
-    hipLaunchKernelGGL(weight_prep_kernel<float>, g, b, 0, s, W, O, C, KW, w_okc, (float*)Wf, ldf,
-                       (float*)Wb, ldb);
-  else return FS2_EINVAL;
-  FS2_CHECK_LAUNCH();
-  return 0;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using U = decltype(t);
+    hipLaunchKernelGGL(weight_prep_kernel<U>, g, b, 0, s, W, O, C, KW, w_okc, (U*)Wf, ldf, (U*)Wb,
+                       ldb);
+  });
 }

@@ -20,7 +20,7 @@
 // bits run to run.
 #include <math.h>
 
-#include "fs2_common.h"
+#include "fs2_launch.h"
 
 namespace {
 
@@ -189,8 +189,6 @@ __global__ void __launch_bounds__(256) bucket_means_kernel(const float* frames,
     }
 }
 
-inline unsigned nblk(long n, int bs = 256) { return (unsigned)((n + bs - 1) / bs); }
-
 }  // namespace
 
 extern "C" int fs2_rank_mixup_input(const float* emo_X, const float* neu_X, const float* lambdas,
@@ -201,15 +199,11 @@ extern "C" int fs2_rank_mixup_input(const float* emo_X, const float* neu_X, cons
   if (n == 0) return 0;
   if (!emo_X || !neu_X || !lambdas || !X || ldx < C) return FS2_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FS2_BF16)
-    hipLaunchKernelGGL(rank_mixup_kernel<bf16>, dim3(nblk(n)), dim3(256), 0, s, emo_X, neu_X,
-                       lambdas, B, T, C, (bf16*)X, ldx, n);
-  else if (dtype == FS2_F32)
-    hipLaunchKernelGGL(rank_mixup_kernel<float>, dim3(nblk(n)), dim3(256), 0, s, emo_X, neu_X,
-                       lambdas, B, T, C, (float*)X, ldx, n);
-  else return FS2_EINVAL;
-  FS2_CHECK_LAUNCH();
-  return 0;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using U = decltype(t);
+    hipLaunchKernelGGL(rank_mixup_kernel<U>, dim3(nblk(n)), dim3(256), 0, s, emo_X, neu_X,
+                       lambdas, B, T, C, (U*)X, ldx, n);
+  });
 }
 
 extern "C" int fs2_rank_pool(const float* I, const int64_t* length, const float* Wp, int B, int T,

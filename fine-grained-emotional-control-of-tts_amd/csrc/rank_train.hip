@@ -21,7 +21,7 @@
 
 #include <algorithm>
 
-#include "fs2_common.h"
+#include "fs2_launch.h"
 
 FS2_SEED_SETTER(fs2_seed_base_rank_train)
 
@@ -317,9 +317,6 @@ __global__ void __launch_bounds__(256) rank_loss_bwd_kernel(
     out[2] = rank;
   }
 }
-
-inline unsigned nblk(long n, int bs = 256) { return (unsigned)((n + bs - 1) / bs); }
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 template <typename TZ, typename T, int BWD>
 void launch_gelu_dropout(const void* Z, int64_t ldz, void* ZA, int64_t ldza, const void* G,

@@ -4,7 +4,7 @@
 //
 // These are HBM-bound integer / gather / segment-reduction kernels (SURVEY K1-K3, K7,
 // K9-K11): coalesced row copies, no MFMA.
-#include "fs2_common.h"
+#include "fs2_launch.h"
 
 namespace {
 
@@ -766,29 +766,16 @@ __global__ void cast_kernel(const S* src, D* dst, long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dst[i] = from_f<D>(to_f(src[i]));
 }
-
-inline unsigned nblk(long n, int bs = 256) { return (unsigned)((n + bs - 1) / bs); }
+template <typename S, typename D>
+void launch_cast(const void* src, void* dst, long n, hipStream_t s) {
+  hipLaunchKernelGGL((cast_kernel<S, D>), dim3(nblk(n)), dim3(256), 0, s, (const S*)src, (D*)dst,
+                     n);
+}
 
 }  // namespace
 
-// every entry point dispatching through DISPATCH_T reports its own launch status (the macro
-// ends in FS2_CHECK_LAUNCH), as do the entry points that launch directly
-#define DISPATCH_T(dtype, KERNEL_CALL_BF16, KERNEL_CALL_F32) \
-  do {                                                     \
-    if ((dtype) == FS2_BF16) { KERNEL_CALL_BF16; }          \
-    else if ((dtype) == FS2_F32) { KERNEL_CALL_F32; }       \
-    else return FS2_EINVAL;                                 \
-    FS2_CHECK_LAUNCH();                                     \
-  } while (0)
-
-// the vectorised row kernels: rows of D columns at a 16-byte aligned base and a
-// row pitch of whole 16-byte vectors
-static bool vec_rows_ok(int dtype, int D, long ld, const void* p0, const void* p1) {
-  const int vn = dtype == FS2_BF16 ? 8 : 4;
-  return D % vn == 0 && ld % vn == 0 && ((uintptr_t)p0 & 15) == 0 && ((uintptr_t)p1 & 15) == 0;
-}
-static int slabs(int dtype, int D) { const int sc = 64 * (dtype == FS2_BF16 ? 8 : 4); return (D + sc - 1) / sc; }
-
+// every entry point reports its own launch status: dispatch_dtype (fs2_launch.h) returns it for
+// the dtype-dispatched launch, FS2_CHECK_LAUNCH for the ones that follow
 
 extern "C" int fs2_embed_fwd(const int64_t* tokens, const float* table, const float* pe,
                              int pad_idx, int B, int T, int D, void* X, float* keep, int dtype,
@@ -798,10 +785,11 @@ extern "C" int fs2_embed_fwd(const int64_t* tokens, const float* table, const fl
   if (n >= 0x7fffffffL) return FS2_EINVAL;   // 32-bit element index
   if (!tokens || !table || !pe || !X || !keep) return FS2_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(embed_fwd_kernel<bf16>, dim3(nblk(n)), dim3(256), 0, s, tokens, table, pe, pad_idx, T, D, (bf16*)X, keep, n),
-    hipLaunchKernelGGL(embed_fwd_kernel<float>, dim3(nblk(n)), dim3(256), 0, s, tokens, table, pe, pad_idx, T, D, (float*)X, keep, n));
-  return 0;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using U = decltype(t);
+    hipLaunchKernelGGL(embed_fwd_kernel<U>, dim3(nblk(n)), dim3(256), 0, s, tokens, table, pe,
+                       pad_idx, T, D, (U*)X, keep, n);
+  });
 }
 
 extern "C" int64_t fs2_embed_bwd_workspace_floats(int D, int V) {
@@ -815,9 +803,12 @@ extern "C" int fs2_embed_bwd(const int64_t* tokens, const void* dX, const float*
   if (!tokens || !dX || !keep || !dtable || !workspace || V < 0) return FS2_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((D + 63) / 64, EMB_CH, (V + EMB_VMAX - 1) / EMB_VMAX);
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(embed_bwd_kernel<bf16>, grid, dim3(256), 0, s, tokens, (const bf16*)dX, keep, M, D, V, workspace),
-    hipLaunchKernelGGL(embed_bwd_kernel<float>, grid, dim3(256), 0, s, tokens, (const float*)dX, keep, M, D, V, workspace));
+  if (int rc = dispatch_dtype(dtype, [&](auto t) {
+        using U = decltype(t);
+        hipLaunchKernelGGL(embed_bwd_kernel<U>, grid, dim3(256), 0, s, tokens, (const U*)dX, keep,
+                           M, D, V, workspace);
+      }))
+    return rc;
   const long n = (long)V * D;
   hipLaunchKernelGGL(embed_bwd_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
                      workspace, EMB_CH, n, dtable);
@@ -853,17 +844,19 @@ extern "C" int fs2_concat_fwd(const void* feats, const float* spk_table, const i
   if (n >= 0x7fffffffL) return FS2_EINVAL;   // 32-bit element index
   if (!feats || !spk_table || !spk || !cat || ldc < 2 * D + E) return FS2_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  if (vec_rows_ok(dtype, D, ldc, feats, cat) && ((uintptr_t)spk_table & 15) == 0) {
+  if (vec_rows_ok(dtype, D, ldc, feats, cat) && aligned16(spk_table)) {
     const int M = B * T;
-    DISPATCH_T(dtype,
-      hipLaunchKernelGGL(concat_fwd_vec_kernel<bf16>, dim3((M + 3) / 4), dim3(256), 0, s, (const bf16*)feats, spk_table, spk, intensity, T, D, E, (bf16*)cat, ldc, M),
-      hipLaunchKernelGGL(concat_fwd_vec_kernel<float>, dim3((M + 3) / 4), dim3(256), 0, s, (const float*)feats, spk_table, spk, intensity, T, D, E, (float*)cat, ldc, M));
-    return 0;
+    return dispatch_dtype(dtype, [&](auto t) {
+      using U = decltype(t);
+      hipLaunchKernelGGL(concat_fwd_vec_kernel<U>, dim3((M + 3) / 4), dim3(256), 0, s,
+                         (const U*)feats, spk_table, spk, intensity, T, D, E, (U*)cat, ldc, M);
+    });
   }
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(concat_fwd_kernel<bf16>, dim3(nblk(n)), dim3(256), 0, s, (const bf16*)feats, spk_table, spk, intensity, T, D, E, (bf16*)cat, ldc, n),
-    hipLaunchKernelGGL(concat_fwd_kernel<float>, dim3(nblk(n)), dim3(256), 0, s, (const float*)feats, spk_table, spk, intensity, T, D, E, (float*)cat, ldc, n));
-  return 0;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using U = decltype(t);
+    hipLaunchKernelGGL(concat_fwd_kernel<U>, dim3(nblk(n)), dim3(256), 0, s, (const U*)feats,
+                       spk_table, spk, intensity, T, D, E, (U*)cat, ldc, n);
+  });
 }
 
 extern "C" int fs2_concat_bwd_spk(const void* dcat, int ldc, const int64_t* spk, int B, int T,
@@ -872,20 +865,23 @@ extern "C" int fs2_concat_bwd_spk(const void* dcat, int ldc, const int64_t* spk,
   if (n_spk == 0 || D == 0 || B == 0) return 0;
   if (!dcat || !spk || !dspk || !workspace) return FS2_EINVAL;
   hipStream_t s = (hipStream_t)stream;
+  int rc;
   if (vec_rows_ok(dtype, D, ldc, dcat, (const char*)dcat + (long)D * (dtype == FS2_BF16 ? 2 : 4))) {
     dim3 grid(B, slabs(dtype, D));
-    DISPATCH_T(dtype,
-      hipLaunchKernelGGL(concat_bwd_utt_vec_kernel<bf16>, grid, dim3(512), 0, s, (const bf16*)dcat, ldc, T, D, workspace),
-      hipLaunchKernelGGL(concat_bwd_utt_vec_kernel<float>, grid, dim3(512), 0, s, (const float*)dcat, ldc, T, D, workspace));
-    hipLaunchKernelGGL(concat_bwd_spk_kernel, dim3(nblk((long)n_spk * D)), dim3(256), 0, s,
-                       workspace, spk, B, D, n_spk, dspk);
-    FS2_CHECK_LAUNCH();
-    return 0;
+    rc = dispatch_dtype(dtype, [&](auto t) {
+      using U = decltype(t);
+      hipLaunchKernelGGL(concat_bwd_utt_vec_kernel<U>, grid, dim3(512), 0, s, (const U*)dcat, ldc,
+                         T, D, workspace);
+    });
+  } else {
+    dim3 grid(B, (D + 63) / 64);
+    rc = dispatch_dtype(dtype, [&](auto t) {
+      using U = decltype(t);
+      hipLaunchKernelGGL(concat_bwd_utt_kernel<U>, grid, dim3(256), 0, s, (const U*)dcat, ldc, T,
+                         D, workspace);
+    });
   }
-  dim3 grid(B, (D + 63) / 64);
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(concat_bwd_utt_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)dcat, ldc, T, D, workspace),
-    hipLaunchKernelGGL(concat_bwd_utt_kernel<float>, grid, dim3(256), 0, s, (const float*)dcat, ldc, T, D, workspace));
+  if (rc) return rc;
   hipLaunchKernelGGL(concat_bwd_spk_kernel, dim3(nblk((long)n_spk * D)), dim3(256), 0, s, workspace,
                      spk, B, D, n_spk, dspk);
   FS2_CHECK_LAUNCH();
@@ -899,10 +895,10 @@ extern "C" int fs2_mask_rows(void* X, int64_t ldx, const float* keep, int M, int
   if (n >= 0x7fffffffL) return FS2_EINVAL;   // 32-bit element index
   if (!X || !keep) return FS2_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(mask_rows_kernel<bf16>, dim3(nblk(n)), dim3(256), 0, s, (bf16*)X, ldx, keep, M, D),
-    hipLaunchKernelGGL(mask_rows_kernel<float>, dim3(nblk(n)), dim3(256), 0, s, (float*)X, ldx, keep, M, D));
-  return 0;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using U = decltype(t);
+    hipLaunchKernelGGL(mask_rows_kernel<U>, dim3(nblk(n)), dim3(256), 0, s, (U*)X, ldx, keep, M, D);
+  });
 }
 
 extern "C" int fs2_add3_mask_rows(void* X, const void* Y, const void* Z, int64_t ld,
@@ -912,10 +908,11 @@ extern "C" int fs2_add3_mask_rows(void* X, const void* Y, const void* Z, int64_t
   if (n >= 0x7fffffffL) return FS2_EINVAL;   // 32-bit element index
   if (!X || !Y || !keep) return FS2_EINVAL;   // Z may be null (a two-term sum)
   hipStream_t s = (hipStream_t)stream;
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(add3_mask_rows_kernel<bf16>, dim3(nblk(n)), dim3(256), 0, s, (bf16*)X, (const bf16*)Y, (const bf16*)Z, ld, keep, M, D),
-    hipLaunchKernelGGL(add3_mask_rows_kernel<float>, dim3(nblk(n)), dim3(256), 0, s, (float*)X, (const float*)Y, (const float*)Z, ld, keep, M, D));
-  return 0;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using U = decltype(t);
+    hipLaunchKernelGGL(add3_mask_rows_kernel<U>, dim3(nblk(n)), dim3(256), 0, s, (U*)X,
+                       (const U*)Y, (const U*)Z, ld, keep, M, D);
+  });
 }
 
 extern "C" int fs2_rowdot_fwd(const void* u, int64_t ldu, const float* w, const float* b,
@@ -924,10 +921,11 @@ extern "C" int fs2_rowdot_fwd(const void* u, int64_t ldu, const float* w, const 
   if (!u || !w || !b || !y) return FS2_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((M + 3) / 4);
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(rowdot_fwd_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)u, ldu, w, b, scale, M, D, (bf16*)y),
-    hipLaunchKernelGGL(rowdot_fwd_kernel<float>, grid, dim3(256), 0, s, (const float*)u, ldu, w, b, scale, M, D, (float*)y));
-  return 0;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using U = decltype(t);
+    hipLaunchKernelGGL(rowdot_fwd_kernel<U>, grid, dim3(256), 0, s, (const U*)u, ldu, w, b, scale,
+                       M, D, (U*)y);
+  });
 }
 
 extern "C" int fs2_rowdot_bwd(const void* dy, const void* u, int64_t ldu, const float* w,
@@ -938,16 +936,22 @@ extern "C" int fs2_rowdot_bwd(const void* dy, const void* u, int64_t ldu, const 
   hipStream_t s = (hipStream_t)stream;
   const int nb = min(256, max(1, (M + 31) / 32));
   const int rpb = (M + nb - 1) / nb;
+  int rc;
   if (vec_rows_ok(dtype, D, ldu, u, du)) {
     dim3 grid(nb, slabs(dtype, D));
-    DISPATCH_T(dtype,
-      hipLaunchKernelGGL(rowdot_bwd_vec_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)dy, (const bf16*)u, ldu, w, scale, M, D, (bf16*)du, workspace, rpb),
-      hipLaunchKernelGGL(rowdot_bwd_vec_kernel<float>, grid, dim3(256), 0, s, (const float*)dy, (const float*)u, ldu, w, scale, M, D, (float*)du, workspace, rpb));
+    rc = dispatch_dtype(dtype, [&](auto t) {
+      using U = decltype(t);
+      hipLaunchKernelGGL(rowdot_bwd_vec_kernel<U>, grid, dim3(256), 0, s, (const U*)dy,
+                         (const U*)u, ldu, w, scale, M, D, (U*)du, workspace, rpb);
+    });
   } else {
-    DISPATCH_T(dtype,
-    hipLaunchKernelGGL(rowdot_bwd_kernel<bf16>, dim3(nb), dim3(256), 0, s, (const bf16*)dy, (const bf16*)u, ldu, w, scale, M, D, (bf16*)du, workspace, rpb),
-    hipLaunchKernelGGL(rowdot_bwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)dy, (const float*)u, ldu, w, scale, M, D, (float*)du, workspace, rpb));
+    rc = dispatch_dtype(dtype, [&](auto t) {
+      using U = decltype(t);
+      hipLaunchKernelGGL(rowdot_bwd_kernel<U>, dim3(nb), dim3(256), 0, s, (const U*)dy,
+                         (const U*)u, ldu, w, scale, M, D, (U*)du, workspace, rpb);
+    });
   }
+  if (rc) return rc;
   hipLaunchKernelGGL(reduce_cols_kernel, dim3((D + 1 + 15) / 16), dim3(256), 0, s, workspace, nb,
                      D + 1, dw, db, D);
   FS2_CHECK_LAUNCH();
@@ -978,15 +982,18 @@ extern "C" int fs2_embed1d_fwd(const void* base, const float* a, const float* W,
   hipStream_t s = (hipStream_t)stream;
   if (vec_rows_ok(dtype, D, D, base, out)) {
     const int M = B * T;
-    DISPATCH_T(dtype,
-      hipLaunchKernelGGL(embed1d_fwd_vec_kernel<bf16>, dim3((M + 4 * EMB1_ROWS - 1) / (4 * EMB1_ROWS)), dim3(256), 0, s, (const bf16*)base, a, W, bias, T, D, KW, (bf16*)out, M),
-      hipLaunchKernelGGL(embed1d_fwd_vec_kernel<float>, dim3((M + 4 * EMB1_ROWS - 1) / (4 * EMB1_ROWS)), dim3(256), 0, s, (const float*)base, a, W, bias, T, D, KW, (float*)out, M));
-    return 0;
+    return dispatch_dtype(dtype, [&](auto t) {
+      using U = decltype(t);
+      hipLaunchKernelGGL(embed1d_fwd_vec_kernel<U>,
+                         dim3((M + 4 * EMB1_ROWS - 1) / (4 * EMB1_ROWS)), dim3(256), 0, s,
+                         (const U*)base, a, W, bias, T, D, KW, (U*)out, M);
+    });
   }
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(embed1d_fwd_kernel<bf16>, dim3(nblk(n)), dim3(256), 0, s, (const bf16*)base, a, W, bias, T, D, KW, (bf16*)out, n),
-    hipLaunchKernelGGL(embed1d_fwd_kernel<float>, dim3(nblk(n)), dim3(256), 0, s, (const float*)base, a, W, bias, T, D, KW, (float*)out, n));
-  return 0;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using U = decltype(t);
+    hipLaunchKernelGGL(embed1d_fwd_kernel<U>, dim3(nblk(n)), dim3(256), 0, s, (const U*)base, a,
+                       W, bias, T, D, KW, (U*)out, n);
+  });
 }
 
 extern "C" int fs2_embed1d_bwd(const void* dout, const float* a, int B, int T, int D, int KW,
@@ -999,18 +1006,24 @@ extern "C" int fs2_embed1d_bwd(const void* dout, const float* a, int B, int T, i
   const int nb = min(128, max(1, (M + 63) / 64));
   const int rpb = (M + nb - 1) / nb;
   if (vec_rows_ok(dtype, D, D, dout, dout)) {
-    DISPATCH_T(dtype,
-      hipLaunchKernelGGL(embed1d_bwd_vec_kernel<bf16>, dim3(nb, slabs(dtype, D)), dim3(512), 0, s, (const bf16*)dout, a, M, T, D, KW, rpb, workspace),
-      hipLaunchKernelGGL(embed1d_bwd_vec_kernel<float>, dim3(nb, slabs(dtype, D)), dim3(512), 0, s, (const float*)dout, a, M, T, D, KW, rpb, workspace));
+    if (int rc = dispatch_dtype(dtype, [&](auto t) {
+          using U = decltype(t);
+          hipLaunchKernelGGL(embed1d_bwd_vec_kernel<U>, dim3(nb, slabs(dtype, D)), dim3(512), 0, s,
+                             (const U*)dout, a, M, T, D, KW, rpb, workspace);
+        }))
+      return rc;
     hipLaunchKernelGGL(reduce_cols_kernel, dim3(((KW + 1) * D + 15) / 16), dim3(256), 0, s,
                        workspace, nb, (KW + 1) * D, dW, dbias, KW * D);
     FS2_CHECK_LAUNCH();
     return 0;
   }
   dim3 grid((D + 255) / 256, nb);
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(embed1d_bwd_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)dout, a, M, T, D, KW, rpb, workspace),
-    hipLaunchKernelGGL(embed1d_bwd_kernel<float>, grid, dim3(256), 0, s, (const float*)dout, a, M, T, D, KW, rpb, workspace));
+  if (int rc = dispatch_dtype(dtype, [&](auto t) {
+        using U = decltype(t);
+        hipLaunchKernelGGL(embed1d_bwd_kernel<U>, grid, dim3(256), 0, s, (const U*)dout, a, M, T,
+                           D, KW, rpb, workspace);
+      }))
+    return rc;
   hipLaunchKernelGGL(embed1d_reduce_kernel, dim3(nblk((long)(KW + 1) * D)), dim3(256), 0, s,
                      workspace, nb, D, KW, dW, dbias);
   FS2_CHECK_LAUNCH();
@@ -1040,16 +1053,18 @@ extern "C" int fs2_lr_gather(const void* X, const int32_t* frame_src, const floa
   if (!X || !frame_src || !pe || !Y) return FS2_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const long Mm = (long)B * Tm;
-  if (Mm < 0x7fffffffL && vec_rows_ok(dtype, D, D, X, Y) && ((uintptr_t)pe & 15) == 0) {
-    DISPATCH_T(dtype,
-      hipLaunchKernelGGL(lr_gather_vec_kernel<bf16>, dim3((Mm + 3) / 4), dim3(256), 0, s, (const bf16*)X, frame_src, pe, Tp, Tm, D, (bf16*)Y, keep, (int)Mm),
-      hipLaunchKernelGGL(lr_gather_vec_kernel<float>, dim3((Mm + 3) / 4), dim3(256), 0, s, (const float*)X, frame_src, pe, Tp, Tm, D, (float*)Y, keep, (int)Mm));
-    return 0;
+  if (Mm < 0x7fffffffL && vec_rows_ok(dtype, D, D, X, Y) && aligned16(pe)) {
+    return dispatch_dtype(dtype, [&](auto t) {
+      using U = decltype(t);
+      hipLaunchKernelGGL(lr_gather_vec_kernel<U>, dim3((Mm + 3) / 4), dim3(256), 0, s,
+                         (const U*)X, frame_src, pe, Tp, Tm, D, (U*)Y, keep, (int)Mm);
+    });
   }
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(lr_gather_kernel<bf16>, dim3(nblk(n)), dim3(256), 0, s, (const bf16*)X, frame_src, pe, Tp, Tm, D, (bf16*)Y, keep, n),
-    hipLaunchKernelGGL(lr_gather_kernel<float>, dim3(nblk(n)), dim3(256), 0, s, (const float*)X, frame_src, pe, Tp, Tm, D, (float*)Y, keep, n));
-  return 0;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using U = decltype(t);
+    hipLaunchKernelGGL(lr_gather_kernel<U>, dim3(nblk(n)), dim3(256), 0, s, (const U*)X,
+                       frame_src, pe, Tp, Tm, D, (U*)Y, keep, n);
+  });
 }
 
 extern "C" int fs2_lr_scatter(const void* dY, const int32_t* cum, const float* keep, int B,
@@ -1059,35 +1074,38 @@ extern "C" int fs2_lr_scatter(const void* dY, const int32_t* cum, const float* k
   hipStream_t s = (hipStream_t)stream;
   if (vec_rows_ok(dtype, D, D, dY, dX)) {
     const int Mp = B * Tp;
-    DISPATCH_T(dtype,
-      hipLaunchKernelGGL(lr_scatter_vec_kernel<bf16>, dim3((Mp + 3) / 4), dim3(256), 0, s, (const bf16*)dY, cum, keep, Tp, Tm, D, (bf16*)dX, Mp),
-      hipLaunchKernelGGL(lr_scatter_vec_kernel<float>, dim3((Mp + 3) / 4), dim3(256), 0, s, (const float*)dY, cum, keep, Tp, Tm, D, (float*)dX, Mp));
-    return 0;
+    return dispatch_dtype(dtype, [&](auto t) {
+      using U = decltype(t);
+      hipLaunchKernelGGL(lr_scatter_vec_kernel<U>, dim3((Mp + 3) / 4), dim3(256), 0, s,
+                         (const U*)dY, cum, keep, Tp, Tm, D, (U*)dX, Mp);
+    });
   }
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(lr_scatter_kernel<bf16>, dim3(B * Tp), dim3(128), 0, s, (const bf16*)dY, cum, keep, Tp, Tm, D, (bf16*)dX),
-    hipLaunchKernelGGL(lr_scatter_kernel<float>, dim3(B * Tp), dim3(128), 0, s, (const float*)dY, cum, keep, Tp, Tm, D, (float*)dX));
-  return 0;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using U = decltype(t);
+    hipLaunchKernelGGL(lr_scatter_kernel<U>, dim3(B * Tp), dim3(128), 0, s, (const U*)dY, cum,
+                       keep, Tp, Tm, D, (U*)dX);
+  });
 }
 
 extern "C" int fs2_fill(void* X, int64_t n, float value, int dtype, void* stream) {
   if (n == 0) return 0;
   if (!X) return FS2_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(fill_kernel<bf16>, dim3(nblk(n)), dim3(256), 0, s, (bf16*)X, (long)n, value),
-    hipLaunchKernelGGL(fill_kernel<float>, dim3(nblk(n)), dim3(256), 0, s, (float*)X, (long)n, value));
-  return 0;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using U = decltype(t);
+    hipLaunchKernelGGL(fill_kernel<U>, dim3(nblk(n)), dim3(256), 0, s, (U*)X, (long)n, value);
+  });
 }
 
 extern "C" int fs2_add(void* X, const void* Y, int64_t n, float alpha, int dtype, void* stream) {
   if (n == 0) return 0;
   if (!X || !Y) return FS2_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(add_kernel<bf16>, dim3(nblk(n)), dim3(256), 0, s, (bf16*)X, (const bf16*)Y, (long)n, alpha),
-    hipLaunchKernelGGL(add_kernel<float>, dim3(nblk(n)), dim3(256), 0, s, (float*)X, (const float*)Y, (long)n, alpha));
-  return 0;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using U = decltype(t);
+    hipLaunchKernelGGL(add_kernel<U>, dim3(nblk(n)), dim3(256), 0, s, (U*)X, (const U*)Y, (long)n,
+                       alpha);
+  });
 }
 
 extern "C" int fs2_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n,
@@ -1095,18 +1113,19 @@ extern "C" int fs2_cast(const void* src, int src_dtype, void* dst, int dst_dtype
   if (n == 0) return 0;
   if (!src || !dst) return FS2_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  const dim3 g(nblk(n)), b(256);
-  if (src_dtype == FS2_F32 && dst_dtype == FS2_BF16)
-    hipLaunchKernelGGL((cast_kernel<float, bf16>), g, b, 0, s, (const float*)src, (bf16*)dst, (long)n);
-  else if (src_dtype == FS2_BF16 && dst_dtype == FS2_F32)
-    hipLaunchKernelGGL((cast_kernel<bf16, float>), g, b, 0, s, (const bf16*)src, (float*)dst, (long)n);
-  else if (src_dtype == FS2_F32 && dst_dtype == FS2_F32)
-    hipLaunchKernelGGL((cast_kernel<float, float>), g, b, 0, s, (const float*)src, (float*)dst, (long)n);
-  else if (src_dtype == FS2_BF16 && dst_dtype == FS2_BF16)
-    hipLaunchKernelGGL((cast_kernel<bf16, bf16>), g, b, 0, s, (const bf16*)src, (bf16*)dst, (long)n);
-  else return FS2_EINVAL;
-  FS2_CHECK_LAUNCH();
-  return 0;
+  // a table, not two nested dispatch_dtype: its order is the order the four kernels are
+  // instantiated in, and so their order in the code object
+  static const struct { int src, dst; void (*launch)(const void*, void*, long, hipStream_t); }
+      CASTS[] = {{FS2_F32, FS2_BF16, launch_cast<float, bf16>},
+                 {FS2_BF16, FS2_F32, launch_cast<bf16, float>},
+                 {FS2_F32, FS2_F32, launch_cast<float, float>},
+                 {FS2_BF16, FS2_BF16, launch_cast<bf16, bf16>}};
+  for (const auto& c : CASTS)
+    if (c.src == src_dtype && c.dst == dst_dtype) {
+      c.launch(src, dst, (long)n, s);
+      return (int)hipGetLastError();
+    }
+  return FS2_EINVAL;
 }
 
 int fs2_seed_base_norm(uint32_t v, void* stream);

@@ -12,7 +12,7 @@
 //   lrelu_kernel           y = leaky_relu(x, slope) (ResBlock1: xt = F.leaky_relu(x, 0.1))
 //   mean3_lrelu_kernel     y = leaky_relu(((a + b) + c) / 3, slope) (the generator's
 //                          z_sum / num_kernels followed by the next stage's leaky ReLU)
-#include "fs2_common.h"
+#include "fs2_launch.h"
 
 namespace {
 
@@ -57,8 +57,6 @@ __global__ void mean3_lrelu_kernel(const T* a, const T* b, const T* c, T* y, lon
   vstore<T>(y + i, va);
 }
 
-inline unsigned nblk(long n, int bs = 256) { return (unsigned)((n + bs - 1) / bs); }
-
 }  // namespace
 
 extern "C" int fs2_vocoder_input(const float* mel, int B, int n_mels, int T, int pad, void* X,
@@ -67,51 +65,38 @@ extern "C" int fs2_vocoder_input(const float* mel, int B, int n_mels, int T, int
   if (n == 0) return 0;
   if (!mel || !X || ldx < n_mels || T < 1 || pad < 0) return FS2_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == FS2_BF16)
-    hipLaunchKernelGGL(vocoder_input_kernel<bf16>, dim3(nblk(n)), dim3(256), 0, s, mel, n_mels, T,
-                       pad, (bf16*)X, ldx, n);
-  else if (dtype == FS2_F32)
-    hipLaunchKernelGGL(vocoder_input_kernel<float>, dim3(nblk(n)), dim3(256), 0, s, mel, n_mels,
-                       T, pad, (float*)X, ldx, n);
-  else return FS2_EINVAL;
-  FS2_CHECK_LAUNCH();
-  return 0;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using U = decltype(t);
+    hipLaunchKernelGGL(vocoder_input_kernel<U>, dim3(nblk(n)), dim3(256), 0, s, mel, n_mels, T,
+                       pad, (U*)X, ldx, n);
+  });
 }
 
 extern "C" int fs2_leaky_relu(const void* x, void* y, int64_t n, float slope, int dtype,
                               void* stream) {
   if (n == 0) return 0;
-  const int V = dtype == FS2_BF16 ? 8 : 4;
-  if (!x || !y || (n % V) || ((uintptr_t)x & 15) || ((uintptr_t)y & 15)) return FS2_EINVAL;
+  const int V = vec_elems(dtype);
+  if (!x || !y || (n % V) || !aligned16(x) || !aligned16(y)) return FS2_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const dim3 g(nblk(n / V));
-  if (dtype == FS2_BF16)
-    hipLaunchKernelGGL(lrelu_kernel<bf16>, g, dim3(256), 0, s, (const bf16*)x, (bf16*)y, (long)n,
-                       slope);
-  else if (dtype == FS2_F32)
-    hipLaunchKernelGGL(lrelu_kernel<float>, g, dim3(256), 0, s, (const float*)x, (float*)y,
-                       (long)n, slope);
-  else return FS2_EINVAL;
-  FS2_CHECK_LAUNCH();
-  return 0;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using U = decltype(t);
+    hipLaunchKernelGGL(lrelu_kernel<U>, g, dim3(256), 0, s, (const U*)x, (U*)y, (long)n, slope);
+  });
 }
 
 extern "C" int fs2_mean3_leaky_relu(const void* a, const void* b, const void* c, void* y,
                                     int64_t n, float slope, int dtype, void* stream) {
   if (n == 0) return 0;
-  const int V = dtype == FS2_BF16 ? 8 : 4;
-  if (!a || !b || !c || !y || (n % V) || (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c |
-                                            (uintptr_t)y) & 15))
+  const int V = vec_elems(dtype);
+  if (!a || !b || !c || !y || (n % V) || !aligned16(a) || !aligned16(b) || !aligned16(c) ||
+      !aligned16(y))
     return FS2_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const dim3 g(nblk(n / V));
-  if (dtype == FS2_BF16)
-    hipLaunchKernelGGL(mean3_lrelu_kernel<bf16>, g, dim3(256), 0, s, (const bf16*)a,
-                       (const bf16*)b, (const bf16*)c, (bf16*)y, (long)n, slope);
-  else if (dtype == FS2_F32)
-    hipLaunchKernelGGL(mean3_lrelu_kernel<float>, g, dim3(256), 0, s, (const float*)a,
-                       (const float*)b, (const float*)c, (float*)y, (long)n, slope);
-  else return FS2_EINVAL;
-  FS2_CHECK_LAUNCH();
-  return 0;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using U = decltype(t);
+    hipLaunchKernelGGL(mean3_lrelu_kernel<U>, g, dim3(256), 0, s, (const U*)a, (const U*)b,
+                       (const U*)c, (U*)y, (long)n, slope);
+  });
 }

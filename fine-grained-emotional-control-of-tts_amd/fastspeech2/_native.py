@@ -197,12 +197,14 @@ _HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "fs2_
 
 def source_hash():
     """SHA-256 (first 16 hex digits) of the library's sources in this tree, in the Makefile's
-    HASH_SRCS order (csrc/*.hip by name, csrc/fs2_common.h, include/fs2_hip.h); None when the
+    HASH_SRCS order (csrc/*.hip by name, csrc/*.h by name, include/fs2_hip.h); None when the
     sources are not present."""
     import hashlib
-    names = sorted(f for f in os.listdir(_CSRC) if f.endswith(".hip")) if os.path.isdir(_CSRC) else []
-    files = [os.path.join(_CSRC, f) for f in names] + [os.path.join(_CSRC, "fs2_common.h"), _HEADER]
-    if not names or not all(os.path.exists(f) for f in files):
+    listing = sorted(os.listdir(_CSRC)) if os.path.isdir(_CSRC) else []
+    names = [f for f in listing if f.endswith(".hip")]
+    files = [os.path.join(_CSRC, f) for f in names + [f for f in listing if f.endswith(".h")]]
+    files.append(_HEADER)
+    if not names or not os.path.exists(_HEADER):
         return None
     h = hashlib.sha256()
     for f in files:

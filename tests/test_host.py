@@ -48,6 +48,27 @@ def test_library_built_from_this_tree_and_stale_build_refused(monkeypatch):
         _native.load(_native.LIB_PATH)
 
 
+def test_source_hash_follows_every_csrc_header(tmp_path, monkeypatch):
+    """source_hash() covers every header of csrc/, not one known by name: a change to any of them
+    changes the hash, so a library built before the change is refused as stale."""
+    import shutil
+    from fastspeech2 import _native
+    csrc = shutil.copytree(_native._CSRC, tmp_path / "csrc",
+                           ignore=shutil.ignore_patterns("build*"))
+    inc = shutil.copytree(os.path.dirname(_native._HEADER), tmp_path / "include")
+    monkeypatch.setattr(_native, "_CSRC", str(csrc))
+    monkeypatch.setattr(_native, "_HEADER", str(inc / "fs2_hip.h"))
+    headers = sorted(csrc.glob("*.h"))
+    assert {"fs2_common.h", "fs2_launch.h", "fs2_cdna.h"} <= {h.name for h in headers}
+    seen = {_native.source_hash()}
+    for h in headers:
+        with open(h, "a") as fh:
+            fh.write(" ")
+        now = _native.source_hash()
+        assert now not in seen, h.name
+        seen.add(now)
+
+
 def test_gemm_host_validation_rejects_bad_args():
     from fastspeech2 import _native as N
     lib = N.load()
@@ -272,6 +293,88 @@ def test_layernorm_host_validation_rejects_bad_args():
     assert slices(ws=p16 + 4) == -1 and slices(out=p16 + 8) == -1   # 16-byte aligned pointers
     assert slices(ws=None) == -1 and slices(out=None) == -1
     assert slices(n=0) == 0
+
+
+def test_every_entry_point_refuses_an_unknown_dtype():
+    """Every entry point that takes a dtype, called with dtype = 2 (neither FS2_F32 = 0 nor
+    FS2_BF16 = 1) and otherwise valid arguments -- non-zero sizes, non-null 16-byte aligned
+    addresses that are never followed -- returns FS2_EINVAL before any launch; the dtype arms of
+    a launcher are written once, so this is the arm neither activation mode reaches.
+    fs2_attn_supported is a predicate and answers 0."""
+    from fastspeech2 import _native as N
+    lib = N.load()
+    buf = (ctypes.c_char * 4096)()
+    p = (ctypes.addressof(buf) + 15) // 16 * 16
+    BAD = 2
+    assert BAD not in (N.F32, N.BF16)
+    calls = {
+        "fs2_conv_fold": (p, 1, 0, 2, 16, 1, 64, p, 64, p, 64, p, p, BAD, None),
+        "fs2_pad_transpose": (p, 64, 2, 16, 64, 1, 1, p, 128, 128, None, None, BAD, None),
+        "fs2_pad_transpose_bounded": (p, 64, 2, 16, 64, 1, 1, p, 128, 128, None, None, p, 1, BAD,
+                                      None),
+        "fs2_pad_rows": (p, 64, 2, 16, 64, 1, 1, 0, p, 64, BAD, None),
+        "fs2_colsum": (p, 64, 16, 64, BAD, p, 0, p, None),
+        "fs2_ln_fwd": (p, 64, None, 0, 0.0, 0, None, p, p, 1e-5, 0, 0.1, 3, None, None, 0, p, 64,
+                       p, p, 16, 64, BAD, 1, None, 0, 0, None),
+        "fs2_ln_bwd": (p, 64, p, 64, p, p, p, p, 0, 0.1, 3, None, 0, p, 64, None, 0.0, 0, None,
+                       None, None, 16, 64, BAD, 1, None, None),
+        "fs2_softmax_fwd": (p, p, 1, 2, 2, 16, 16, 16, 0.5, 0.1, 1, 2, p, p, BAD, None),
+        "fs2_softmax_bwd": (p, p, 2, 2, 16, 16, 16, 0.5, 0.1, 1, 2, p, BAD, None),
+        "fs2_attn_fwd": (p, 384, p, 1, 2, 2, 16, 64, 0.125, 0.1, 1, 2, p, 128, p, BAD, None),
+        "fs2_attn_bwd": (p, 384, p, 1, p, 128, p, 128, p, 2, 2, 16, 64, 0.125, 0.1, 1, 2, p, 384,
+                         p, BAD, None),
+        "fs2_attn_bwd_bounded": (p, 384, p, 1, p, 128, p, 128, p, 2, 2, 16, 64, 0.125, 0.1, 1, 2,
+                                 p, 384, p, p, BAD, None),
+        "fs2_embed_fwd": (p, p, p, 0, 2, 16, 64, p, p, BAD, None),
+        "fs2_embed_bwd": (p, p, p, 32, 64, 8, p, p, BAD, None),
+        "fs2_concat_fwd": (p, p, p, p, 2, 16, 64, 4, p, 136, BAD, None),
+        "fs2_concat_bwd_spk": (p, 136, p, 2, 16, 64, 4, p, BAD, p, None),
+        "fs2_mask_rows": (p, 64, p, 16, 64, BAD, None),
+        "fs2_add3_mask_rows": (p, p, p, 64, p, 16, 64, BAD, None),
+        "fs2_rowdot_fwd": (p, 64, p, p, 1.0, 16, 64, p, BAD, None),
+        "fs2_rowdot_bwd": (p, p, 64, p, 1.0, 16, 64, p, p, p, BAD, p, None),
+        "fs2_embed1d_fwd": (p, p, p, p, 2, 16, 64, 3, p, BAD, None),
+        "fs2_embed1d_bwd": (p, p, 2, 16, 64, 3, p, p, BAD, p, None),
+        "fs2_lr_gather": (p, p, p, 2, 8, 16, 64, p, p, BAD, None),
+        "fs2_lr_scatter": (p, p, p, 2, 8, 16, 64, p, BAD, None),
+        "fs2_weight_prep": (p, 16, 16, 3, 0, p, 48, p, 48, BAD, None),
+        "fs2_weight_prep_batched": (p, 1, 1, BAD, None),
+        "fs2_adamw_prep": (p, 1, 1, p, 1, 1, p, p, p, p, 1.0, 0.1, 0.999, 0.001, 1e-3, 1.0, 1e-8,
+                           1.0, BAD, None),
+        "fs2_intensity_input": (p, 1, 2, 16, 80, p, 96, BAD, None),
+        "fs2_intensity_head": (p, 64, p, p, p, p, p, 2, 16, 64, 4, p, BAD, None),
+        "fs2_rank_mixup_input": (p, p, p, 2, 16, 80, p, 96, BAD, None),
+        "fs2_gelu_dropout_fwd": (p, 64, 0, p, 64, p, 64, 16, 64, 0.1, 1, 2, BAD, None),
+        "fs2_gelu_dropout_bwd": (p, 64, p, 64, p, 64, 16, 64, 0.1, 1, 2, BAD, None),
+        "fs2_intensity_head_bwd": (p, p, 64, p, p, 4, p, p, 2, 16, 64, 4, p, 64, p, p, p, p, BAD,
+                                   None),
+        "fs2_vocoder_input": (p, 2, 80, 16, 3, p, 96, BAD, None),
+        "fs2_leaky_relu": (p, p, 64, 0.1, BAD, None),
+        "fs2_mean3_leaky_relu": (p, p, p, p, 64, 0.1, BAD, None),
+        "fs2_fill": (p, 64, 0.0, BAD, None),
+        "fs2_add": (p, p, 64, 1.0, BAD, None),
+    }
+    for name, args in calls.items():
+        assert len(args) == len(N.SIGNATURES[name][1]), name
+        assert getattr(lib, name)(*args) == -1, name
+    for src, dst in ((BAD, N.F32), (N.BF16, BAD), (BAD, BAD)):
+        assert lib.fs2_cast(p, src, p, dst, 64, None) == -1, (src, dst)
+    assert lib.fs2_attn_supported(16, 64, BAD) == 0
+    # the descriptors' dtype: the GEMM's checks take every dtype but bf16 for fp32 and its planner
+    # refuses it; the loss refuses it after its pointer checks
+    g = N.GemmDesc(M=16, N=16, K=16, dtype=BAD, A=p, lda=16, a_kmajor=1, B=p, ldb=16, b_kmajor=1,
+                   C=p, ldc=16)
+    assert lib.fs2_gemm(ctypes.byref(g), None) == -1
+    assert lib.fs2_gemm_plan(ctypes.byref(g), ctypes.byref(N.GemmPlanInfo())) == -1
+    ld = N.LossDesc(B=2, Tm=16, Tp=8, NM=80, dtype=BAD,
+                    **{f: p for f, t in N.LossDesc._fields_ if t is ctypes.c_void_p})
+    assert lib.fs2_loss_fwd_bwd(ctypes.byref(ld), None) == -1
+    # every prototype with a dtype parameter is covered above
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "fs2_hip.h")).read(),
+                 flags=re.S)
+    takes = {n for n, a in re.findall(r"\b(fs2_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", src, flags=re.S)
+             if re.search(r"\bint (src_)?dtype\b", a)}
+    assert takes == set(calls) | {"fs2_cast", "fs2_attn_supported"}
 
 
 def test_ctypes_argument_counts_match_header():
