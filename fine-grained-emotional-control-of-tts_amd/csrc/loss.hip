@@ -72,13 +72,15 @@ __device__ __forceinline__ float block_min(float v, float* sh) {
   return s;
 }
 
-__device__ __forceinline__ float gauss1(int i) {
-  // normalised 1-D Gaussian tap; the 2-D window of gaussian_filter() is its outer product
-  float s = 0.f;
-  for (int k = 0; k < WIN; ++k) { const float c = k - 5.f; s += expf(-(c * c) / 4.5f); }
-  const float c = i - 5.f;
-  return expf(-(c * c) / 4.5f) / s;
-}
+// Normalised 1-D Gaussian taps exp(-(i - 5)^2 / 4.5) / sum, evaluated in double and rounded to
+// fp32; the 2-D window of gaussian_filter() is their outer product.  They sum to 1 - 1.4e-9.
+// Taps normalised by an fp32 sum of expf() summed to 1 + 6e-8, and sigma = E[x^2] - mu^2
+// amplifies a window whose weights do not sum to 1: that alone put 1e-5 of the utterance's
+// maximum into the SSIM gradient.
+__constant__ float GAUSS1[WIN] = {0.00102838012f, 0.00759875821f, 0.0360007733f, 0.109360687f,
+                                  0.213005543f,   0.266011715f,   0.213005543f,  0.109360687f,
+                                  0.0360007733f,  0.00759875821f, 0.00102838012f};
+__device__ __forceinline__ float gauss1(int i) { return GAUSS1[i]; }
 
 // ---- 1: MSE terms + their gradients -------------------------------------------------------
 template <typename T>
@@ -310,15 +312,22 @@ __global__ void __launch_bounds__(256) ssim_map_kernel(LossP p) {
       eyy += w * hs[3][ti + di][j]; exy += w * hs[4][ti + di][j];
     }
     const float sxx = exx - a * a, syy = eyy - bb * bb, sxy = exy - a * bb;
-    const float L1 = 2.f * a * bb + C1, D1 = a * a + bb * bb + C1;
+    // D1 = a^2 + b^2 + C1 taken as L1 + (a - b)^2: equal means give L1 = D1 bit for bit (with
+    // FMA contraction 2ab + C1 and a^2 + b^2 + C1 round differently), so lum = 1 and
+    // dl_db = 0 there; an ulp between them is 4e-6 in dl_db where the means are near 0.007
+    const float dab = a - bb;
+    const float L1 = 2.f * a * bb + C1, D1 = L1 + dab * dab;
     const float N2 = 2.f * sxy + C2, D2 = sxx + syy + C2;
-    const float cs = N2 / D2;
-    ss += (L1 / D1) * cs;
-    const float dl_db = (2.f * a * D1 - L1 * 2.f * bb) / (D1 * D1);
-    const float dn_db = (-2.f * a * D2 + 2.f * bb * N2) / (D2 * D2);
-    const float Db = cs * dl_db + (L1 / D1) * dn_db;
-    const float Deyy = (L1 / D1) * (-N2 / (D2 * D2));
-    const float Dexy = (L1 / D1) * (2.f / D2);
+    const float cs = N2 / D2, lum = L1 / D1;
+    ss += lum * cs;
+    // d(cs)/d(syy) = -cs / D2 and d(cs)/d(sxy) = 2 / D2 share q = lum / D2: where prediction
+    // and target agree (cs = 1) the two planes are exactly -q and 2 q and cancel in
+    // ssim_grad_kernel term by term, as they do in autograd; -N2 / D2^2 did not
+    const float q = lum / D2;
+    const float dl_db = 2.f * (a - bb * lum) / D1;
+    const float Db = cs * dl_db + 2.f * q * (bb * cs - a);
+    const float Deyy = -cs * q;
+    const float Dexy = 2.f * q;
     const long o = (long)b * p.npix + (long)i * OW + j;
     p.dmap[o] = Db; p.dmap[plane + o] = Deyy; p.dmap[2 * plane + o] = Dexy;
   }
@@ -439,7 +448,9 @@ __global__ void __launch_bounds__(256) ssim_grad_kernel(LossP p) {
     float X, Y;
     norm_xy<T>(p, nc, b, t, f, X, Y);
     float dn = 0.f;
-    if (t < L) dn = g * (U + 2.f * Y * V + X * W);
+    // 2 Y V + X W as X (W + 2 V) + 2 V (Y - X): both brackets vanish exactly where Y = X and
+    // W = -2 V, whether or not the compiler contracts the products into FMAs
+    if (t < L) dn = g * (U + X * (W + 2.f * V) + 2.f * V * (Y - X));
     const long q = (long)t * NM + f;
     p.dnmap[(long)b * Tm * NM + q] = dn;
     if (t < L) {

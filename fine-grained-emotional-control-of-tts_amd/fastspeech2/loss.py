@@ -51,7 +51,7 @@ def fused_loss(mel_out, postnet_out, log_dur, pitch_pred, energy_pred, mel_tgt, 
     g_dur = torch.empty(B, Tp, dtype=mel_out.dtype, device=dev)
     g_pitch = torch.empty(B, Tp, dtype=mel_out.dtype, device=dev)
     g_energy = torch.empty(B, Tp, dtype=mel_out.dtype, device=dev)
-    ws = torch.empty(int(ops.loss_ws(B, Tm, NM)) + 64, dtype=torch.float32, device=dev)
+    ws = torch.empty(int(ops.loss_ws(B, Tm, NM)), dtype=torch.float32, device=dev)
     d.loss_out = loss.data_ptr()
     d.d_mel_out, d.d_postnet_out = g_mel.data_ptr(), g_post.data_ptr()
     d.d_log_dur, d.d_pitch, d.d_energy = g_dur.data_ptr(), g_pitch.data_ptr(), g_energy.data_ptr()
