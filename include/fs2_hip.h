@@ -401,7 +401,13 @@ int fs2_weight_prep_batched(const fs2_wprep_desc* descs, int n, int total_tiles,
  * optimiser step, K17 of SURVEY §2): the descriptor table's weights are updated tile by tile
  * and their Wf / Wb images written from the updated values; every other parameter lies in
  * `ranges` (int64 triples: flat start, length, first block; 1024 elements per block).  All
- * pointers index the same flat layout: descs[i].W - param is a weight's flat offset. */
+ * pointers index the same flat layout: descs[i].W - param is a weight's flat offset.
+ * Every master is read as [O][KW][C] (element (o, j, c) at W[(o*KW + j)*C + c]) whatever bit 0
+ * of w_okc says: it must be set whenever KW > 1 (with KW == 1 the two layouts coincide), or the
+ * images come out wrong without an error -- fs2_weight_prep_batched honours the bit, this call
+ * does not.  Wb's columns from KW*O up to ldb are not written (fs2_weight_prep zeroes them).
+ * param, grad, exp_avg and exp_avg_sq must be 16-byte aligned: the 16-byte form of a tile is
+ * chosen from the weight's flat offset and pitches alone. */
 int fs2_adamw_prep(const fs2_wprep_desc* descs, int n, int total_tiles, const int64_t* ranges,
                    int n_ranges, int range_blocks, float* param, const float* grad,
                    float* exp_avg, float* exp_avg_sq, float decay_mul, float one_minus_beta1,

@@ -1225,6 +1225,16 @@ def test_weight_prep_reversed_taps(cuda):
     ops.weight_prep(W, O, C, KW, Wf, ldf, Wb, KW * O, dt=1, w_okc=3)
     torch.cuda.synchronize()
     assert torch.equal(Wb, ref_b)
+    # the fused AdamW image pass, zero step: W is the whole flat parameter buffer
+    Wf.fill_(float("nan"))
+    Wb.fill_(float("nan"))
+    W0 = W.clone()
+    g, m, v = (torch.zeros(O * KW * C, device=cuda) for _ in range(3))
+    ops.adamw_prep(table, ops.adamw_ranges_table([], cuda), W.view(-1), g, m, v,
+                   1.0, 0.1, 0.999, 0.001, 0.0, 1.0, 1e-8, 1.0, dt=1)
+    torch.cuda.synchronize()
+    assert torch.equal(W, W0) and not m.any() and not v.any() and not g.any()
+    assert torch.equal(Wf, ref_f) and torch.equal(Wb, ref_b)
 
 
 @pytest.mark.parametrize("O,C,KW", [(1536, 384, 9), (192, 72, 5), (128, 40, 3), (256, 128, 9)])
