@@ -19,11 +19,10 @@ import re
 import torch
 
 from . import _native as N
+from . import lowering
 from . import ops
 from .attention import attention_bwd, attention_fwd, use_flash
-from .ops import round_up
-
-BK = {N.F32: 32, N.BF16: 64}
+from .lowering import BK, dgrad_split, eff_split, ps_plain_ok, round_up, wgrad_slices  # noqa: F401
 
 
 class _Salt:
@@ -35,47 +34,6 @@ class _Salt:
         return self.n
 
 
-def dgrad_split(Mp, C, K, dt, n_cu=256, max_split=8):
-    """K split for the shift-conv data gradient, chosen for wave quantisation over the 256 CUs
-    (one 256x128 tile per CU at a time): the decoder's 372 tiles fill 1.45 rounds (73 %), two
-    slices fill 2.9 (97 %); the encoder's 78 tiles fill 30 %, three slices 91 %.  Slices are
-    fp32 planes summed by fs2_conv_fold, so a split must gain > 5 % occupancy to pay for its
-    extra plane."""
-    if dt != 1:
-        return 1
-    if K >= 2048 and C >= 128 and C % 4 == 0:
-        # the persistent 256 x 192 / 256 x 256 kernel (gemm_ps_kernel) takes an unsplit data
-        # gradient when its tiles fill most of one round (the decoder: 124 x 2 = 248 tiles)
-        w = 192 if C % 256 and -(-C // 192) * 192 < -(-C // 256) * 256 else 256
-        if -(-Mp // 256) * -(-C // w) >= 200:
-            return 1
-    tiles = -(-Mp // 256) * -(-C // 128)
-
-    def eff(s):
-        return tiles * s / (n_cu * -(-(tiles * s) // n_cu))
-
-    best, best_eff = 1, eff(1)
-    for s in range(2, max(1, min(max_split, (K // 64) // 8)) + 1):
-        if eff(s) > best_eff + 0.05:
-            best, best_eff = s, eff(s)
-    return best
-
-
-# large weight gradients (the FFN conv1 weights, 5.3 M floats) as split-K planes + fixed-order
-# sum instead of split-K fp32 atomics: decoder 428 -> 420 us, encoder 128 -> 119 us, and the
-# result no longer depends on atomic ordering.  (tile, slice) units they aim for:
-_SLICE_TARGET = 240
-# CU budget of the small weight gradients' split-K on the side stream: sliced ones fill
-# _WG_SLICE_CU CUs, the atomic ones _WG_ATOMIC_UNITS (tile, split) units
-_WG_SLICE_CU = 256
-_WG_ATOMIC_UNITS = 512
-# decoder FFN conv1 data gradient in the tap-inner K order (engine._tap_inner): off -- 11 %
-# faster standalone and 190 instead of 995 MB read, but the step measured 0.03-0.08 ms slower
-# with it in three same-box A/Bs (17.18 vs 17.13 ms on the final tree); the FFN conv1 forward in
-# that order (engine._tap_inner_fwd): off -- 316-318 vs 314 us for the decoder's in the step,
-# step 17.42 vs 17.37 ms (experiments library, 2 x 2 interleaved)
-_TAP_INNER = N.exp_int("FS2_TAP_INNER", 0)
-_TAP_INNER_FWD = N.exp_int("FS2_TAP_INNER_FWD", 0)
 # serial mode for per-call-site timing (bench.py --detail runs with the experiments library)
 _NO_SIDE = N.exp_flag("FS2_NO_SIDE_STREAM")
 _NO_AUX = N.exp_flag("FS2_NO_AUX_STREAM")
@@ -85,43 +43,6 @@ _NO_AUX = N.exp_flag("FS2_NO_AUX_STREAM")
 # (DESIGN.md section 6.7, 2 x 7 interleaved bench runs): 256 -> 18.23-18.29 ms, 176-240 ->
 # 18.01-18.13, 160 -> 18.87; 208 kept.
 _SIDE_CTAS = 208
-
-
-def ps_plain_ok(M, lda, N, ldb, out_rows, ldc, out_bytes):
-    """fs2_gemm can take a padded-domain GEMM (c_row output remap) only on its persistent
-    kernel, with every operand within the kernel's 32-bit buffer offsets -- otherwise the engine
-    keeps the implicit-conv path instead of handing fs2_gemm a call it refuses."""
-    lim = 0x7fffffff
-    return M * lda * 2 < lim and N * ldb * 2 < lim and out_rows * ldc * out_bytes < lim
-
-
-def eff_split(K, ns, bk):
-    """the split-K slice count fs2_gemm actually uses for ``ns`` requested slices of K (it
-    rounds the K-tiles per slice up, which can leave trailing slices empty -- those it zeroes
-    with a memset so a consumer summing all ``ns`` stays right).  Requesting this count instead
-    skips the memset launch."""
-    if ns <= 1:
-        return 1
-    nkt = -(-K // bk)
-    return -(-nkt // -(-nkt // ns))
-
-
-def wgrad_slices(O, Ncols, ldc, K, dt, n_cu=256):
-    """Split-K slice count for a weight gradient with a small output: enough 256x128 tiles x
-    slices to fill the 256 CUs once, each slice >= 8 K-tiles; slices are fp32 planes summed in
-    a fixed order instead of tens of fp32 atomics landing on every output element.  Applied
-    where it measured faster (bench.py --detail): outputs of
-    >= 256 rows and <= 256 K elements (out-projection 62 -> 55 us, PostNet conv_pre 73 -> 57 us),
-    or <= 600 K elements over encoder-length K (conv2 58 -> 42 us, out-projection 47 -> 31 us).
-    1 = the atomic split-K path (decoder conv2 91 vs 144 us, PostNet 150 vs 231 us)."""
-    if dt != 1 or ldc % 8 or Ncols != ldc or O < 256:
-        return 1
-    n = O * ldc
-    if not (n <= (1 << 18) or (n <= 600_000 and K <= 8192)):
-        return 1
-    tiles = -(-O // 256) * -(-Ncols // 128)
-    ns = min(-(-n_cu // tiles), max(1, (K // 64) // 8))
-    return ns if ns >= 2 else 1
 
 
 class FS2Engine:
@@ -242,24 +163,22 @@ class FS2Engine:
         return img
 
     def _tic(self, tag):
-        if self.timer is not None:
+        if tag and self.timer is not None:
             self.timer.start(tag)
 
     def _toc(self, tag):
-        if self.timer is not None:
+        if tag and self.timer is not None:
             self.timer.stop(tag)
 
     @contextlib.contextmanager
     def _timed(self, kind, T):
         """the detailed timer's tag around the attention block's fused kernel launch"""
         tag = self._dtag(kind, "", T)
-        if tag:
-            self._tic(tag)
+        self._tic(tag)
         try:
             yield
         finally:
-            if tag:
-                self._toc(tag)
+            self._toc(tag)
 
     # ------------------------------------------------------------------ helpers
     def use_flash(self, T, dh):
@@ -361,8 +280,9 @@ class FS2Engine:
         f, gf = self.m._flat, self.m._gflat
         ow, nw = lay[wd][0], 2 * lay[wd][1]
         ob = lay[bd][0]
-        del self._wspecs[wd], self._wspecs[wp]
+        del self._wspecs[wd], self._wspecs[wp], self._okc[wd], self._okc[wp]
         self._wspecs[self.PRED1] = (2 * O, C, KW)
+        self._okc[self.PRED1] = lowering.w_okc(self.PRED1, 2 * O, C, KW, self.dt)
         self.params[self.PRED1 + ".weight"] = f[ow:ow + nw].view(2 * O, KW, C).permute(0, 2, 1)
         self.grads[self.PRED1] = gf[ow:ow + nw].view(2 * O, KW, C).permute(0, 2, 1)
         self.params[self.PRED1 + ".bias"] = f[ob:ob + 2 * O]
@@ -371,7 +291,7 @@ class FS2Engine:
         del self.grads[wd], self.grads[wp]
 
     def _weight_specs(self):
-        """name -> (O, C, KW, ldf, ldb_rows) for every GEMM weight."""
+        """name -> (O, C, KW) of every GEMM weight; self._okc: its weight images, decided once"""
         c = self.cfg
         D = c.enc_d_model
         specs = {}
@@ -395,6 +315,7 @@ class FS2Engine:
         for i in range(c.postnet_n_convolutions - 2):
             specs[f"postnet.convs_intermedite.{i}.conv.weight"] = (E, E, KP)
         specs["postnet.conv_post.conv.weight"] = (c.n_mels, E, KP)
+        self._okc = {n: lowering.w_okc(n, *s, self.dt) for n, s in specs.items()}
         return specs
 
     def prepare_weights(self, force=False):
@@ -415,14 +336,7 @@ class FS2Engine:
                     self.w[name] = (self.empty(O, ldf), self.empty(C, ldb))
                 Wf, Wb = self.w[name]
                 W = self.params[name + ".weight" if name == self.PRED1 else name]
-                # conv weights are [O][KW][C] in the flat buffer (model._kw_major); the FFN
-                # conv1 data-gradient image has its taps reversed on the padded-dY path, and
-                # its columns in tap-inner 64-channel chunks where that GEMM reads the image
-                # in that order (_tap_inner)
-                okc = int(KW > 1) | (2 if self._pad_dgrad(name) else 0) | \
-                    (4 if self._tap_inner(name) else 0) | \
-                    (8 if self._tap_inner_fwd(name) else 0)
-                entries.append((W, O, C, KW, okc, Wf, ldf, Wb, ldb))
+                entries.append((W, O, C, KW, self._okc[name], Wf, ldf, Wb, ldb))
                 self._wentries[name] = entries[-1]
             self._wtable = ops.weight_prep_table(entries)
         ops.weight_prep_batched(*self._wtable, dt=self.dt)
@@ -529,94 +443,28 @@ class FS2Engine:
         O, C, KW = self._wspecs[wname]
         Wf, _ = self.w[wname]
         K = Wf.shape[1]
-        conv = (1, T, KW, C) if KW > 1 else None
+        ti = self._okc[wname] & lowering.W_TAP_INNER_FWD
         tag = self._dtag("fwd", wname, T)
-        if tag:
-            self._tic(tag)
-        ti = self._tap_inner_fwd(wname)
+        self._tic(tag)
         if isinstance(X, tuple):
-            # reflect-padded X image (_pad_fwd): the conv over the padded domain is a plain
-            # K-major GEMM with overlapping rows, A(m, k=(j,c)) = image[m*C + k] (in the
-            # tap-inner order with a Wf built that way, fs2_gemm_desc.a_kw); the pad rows'
-            # results are dropped by the epilogue (c_row = (T, -2P))
+            # reflect-padded X image (lowering.fwd_padded): a plain K-major GEMM with overlapping
+            # rows, A(m, k=(j,c)) = image[m*C + k]; the epilogue drops the pad rows' results
             P = (KW - 1) // 2
-            Mp = (M // T) * (T + 2 * P)
-            ops.gemm(Mp, O, K, X[0], C, Wf, K, out, ldo, dt=self.dt, c_row=(T, -2 * P),
-                     a_kw=KW if ti else 0, **epi)
+            ops.gemm((M // T) * (T + 2 * P), O, K, X[0], C, Wf, K, out, ldo, dt=self.dt,
+                     c_row=(T, -2 * P), a_kw=KW if ti else 0, **epi)
         else:
             if ti:
                 raise ValueError(f"{wname}: its forward image is in the tap-inner order of the "
                                  "padded-image path, which this batch cannot take")
-            ops.gemm(M, O, K, X, ldx, Wf, K, out, ldo, dt=self.dt, conv=conv, **epi)
-        if tag:
-            self._toc(tag)
-
-    def _pad_fwd(self, wname, M, T):
-        """FFN conv1 forward over a reflect-padded token-major X image (fs2_pad_rows + a plain
-        GEMM whose A rows overlap, 2P dropped rows per utterance): tools/fwd_probe.py, B = 32:
-        decoder 374 -> 305 us, encoder 100 -> 89 standalone (the implicit conv's per-K-tile
-        reflect rows and tap offsets are gone from the loader)"""
-        O, C, KW = self._wspecs[wname]
-        # both stacks: over the image the decoder's conv1 is a plain GEMM for the 4-wave kernel
-        # (gemm_w4b_kernel), step 17.54 -> 17.35 ms on one box (tools/step_ab.sh, 3 rounds);
-        # on the 8-wave implicit conv it had measured no faster.
-        P = (KW - 1) // 2
-        if self._tap_inner_fwd(wname):   # the 4-wave kernel: 32-bit offsets to 2.8 M rows
-            return P < T
-        return (self.dt == 1 and KW > 1 and C % 64 == 0 and P < T and
-                self.w[wname][0].shape[1] == KW * C and
-                ps_plain_ok((M // T) * (T + 2 * P), C, O, KW * C, M, O, 2))
+            ops.gemm(M, O, K, X, ldx, Wf, K, out, ldo, dt=self.dt,
+                     conv=(1, T, KW, C) if KW > 1 else None, **epi)
+        self._toc(tag)
 
     def _dgrad(self, dY, lddy, M, T, wname, out, ldo, n_out=None, **epi):
         tag = self._dtag("dgrad", wname, T)
-        if tag:
-            self._tic(tag)
+        self._tic(tag)
         self._dgrad_impl(dY, lddy, M, T, wname, out, ldo, n_out, **epi)
-        if tag:
-            self._toc(tag)
-
-    def _pad_dgrad(self, wname):
-        """FFN conv1 data gradients over a zero-padded token-major dY image (bf16): the
-        producing conv2 data gradient writes dY into the image (fs2_gemm c_row_t), and with the
-        weight image's taps reversed the shift conv is a plain K-major GEMM whose A rows
-        overlap, A(m, k) = image[m * O + k] (tools/dgrad_probe.py, B = 32: decoder 417 -> 339
-        us, encoder 83 -> 76) -- no per-K-tile tap offsets or row bounds in the loader."""
-        if self.dt != 1 or ".pos_ffn.0." not in wname:
-            return False
-        O, C, KW = self._wspecs[wname]
-        return KW > 1 and self._km_ok(O, C, KW, KW, None)
-
-    def _tap_inner(self, wname):
-        """the decoder FFN conv1 data gradient over the padded dY image in the tap-inner K order
-        (fs2_gemm_desc.a_kw, Wb built with w_okc bit 2): consecutive 64-deep K-stages read image
-        rows one tap apart, so the 96 MB image is fetched from HBM about once instead of once
-        per tap (995 MB per launch in the natural order, profiles/r05e_dgrad_traffic.json).
-        Always the 4-wave kernel, unsplit; the encoder's (M = 6656) keeps its split-K path."""
-        if not (_TAP_INNER and self._pad_dgrad(wname) and wname.startswith("decoder.")):
-            return False
-        O, C, KW = self._wspecs[wname]
-        return O % 64 == 0 and (KW * O) % 128 == 0
-
-    def _tap_inner_fwd(self, wname):
-        """the FFN conv1 forward over the reflect-padded X image in the tap-inner K order (Wf
-        built with w_okc bit 3), both stacks: the image's rows are fetched about once instead of
-        once per tap.  Needs the padded path on every batch (_pad_fwd's conditions other than
-        P < T, which the reference's reflect padding requires anyway)."""
-        if not (_TAP_INNER_FWD and self.dt == 1 and ".pos_ffn.0." in wname):
-            return False
-        O, C, KW = self._wspecs[wname]
-        return KW > 1 and C % 64 == 0 and (KW * C) % 128 == 0 and \
-            self.w[wname][0].shape[1] == KW * C
-
-    def _pad_dgrad_fits(self, wname, B, T):
-        """the padded data gradient's GEMM within the persistent kernel's 32-bit offsets"""
-        O, C, KW = self._wspecs[wname]
-        P = (KW - 1) // 2
-        Mp = B * (T + 2 * P)
-        # the image (Mp + 2P rows of O), the weight image, the fp32 padded-domain output, and
-        # conv2's data gradient written into the image (c_row = (T, 2P))
-        return (ps_plain_ok(Mp + 2 * P, O, C, KW * O, Mp, C, 4) and
-                ps_plain_ok(B * T, O, O, O, Mp + 2 * P, O, 2))
+        self._toc(tag)
 
     def _dy_image(self, key, B, T, P, F):
         """zero-padded token-major image for a k = 2P+1 conv data gradient: 2P zero rows, then
@@ -659,25 +507,21 @@ class FS2Engine:
         P = (KW - 1) // 2
         B = M // T
         Mp = B * (T + 2 * P)
-        ti = isinstance(dY, tuple) and self._tap_inner(wname)
-        split = 1 if ti else dgrad_split(Mp, C, KW * O, self.dt)
+        ti = isinstance(dY, tuple) and self._okc[wname] & lowering.W_TAP_INNER
+        split = 1 if ti else lowering.dgrad_split(Mp, C, KW * O, self.dt)
+        stride = Mp * C if split > 1 else 0
         Xpad = torch.empty(split, Mp, C, dtype=torch.float32, device=self.dev)
         if isinstance(dY, tuple):
             # padded dY image (_dy_image): row m of the padded domain reads image rows
             # m .. m + 2P, i.e. A(m, k) = image[m * O + k] against the tap-reversed Wb (in the
             # tap-inner order: k = (64-channel chunk, tap, channel), fs2_gemm_desc.a_kw)
-            img = dY[0]
-            ops.gemm(Mp, C, KW * O, img, O, Wb, KW * O, Xpad, C, dt=self.dt, c_fp32=1,
-                     split_k=split, split_stride=Mp * C if split > 1 else 0,
-                     a_kw=KW if ti else 0)
+            ops.gemm(Mp, C, KW * O, dY[0], O, Wb, KW * O, Xpad, C, dt=self.dt, c_fp32=1,
+                     split_k=split, split_stride=stride, a_kw=KW if ti else 0)
         else:
-            ops.gemm(Mp, C, KW * O, dY, lddy, Wb, KW * O, Xpad, C, dt=self.dt, conv=(4, T, KW, O),
-                     c_fp32=1, split_k=split, split_stride=Mp * C if split > 1 else 0)
-        assert set(epi) <= {"residual", "ldr", "row_scale", "row_scale_post"}, epi
-        ops.conv_fold(Xpad, B, T, P, C, out, ldo, dt=self.dt, residual=epi.get("residual"),
-                      ldr=epi.get("ldr", 0), row_scale=epi.get("row_scale"),
-                      row_scale_post=epi.get("row_scale_post"), nsplit=split,
-                      split_stride=Mp * C)
+            ops.gemm(Mp, C, KW * O, dY, lddy, Wb, KW * O, Xpad, C, dt=self.dt,
+                     conv=(4, T, KW, O), c_fp32=1, split_k=split, split_stride=stride)
+        ops.conv_fold(Xpad, B, T, P, C, out, ldo, dt=self.dt, nsplit=split, split_stride=Mp * C,
+                      **epi)
 
     def _wgrad(self, dY, lddy, X, ldx, M, T, wname, n_cols=None, gemm_tag=None, bias=None,
                dy_img=None, grad_end=None):
@@ -689,26 +533,15 @@ class FS2Engine:
                                     T + self._wspecs[wname][2] - 1 if dy_img is not None else None)
         h = self._side_enter(dY, X, dy_img, grad_end)
         tag = self._dtag("wgrad", wname, T)
-        if tag:
-            self._tic(tag)
+        self._tic(tag)
         ctas = self._side_ctas if h is not None else 0
         done = self._wgrad_impl(dY, lddy, X, ldx, M, T, wname, n_cols, gemm_tag, bias, dy_img,
                                 ctas, grad_end)
-        if tag:
-            self._toc(tag)
+        self._toc(tag)
         if bias is not None and not done:
             O = self._wspecs[wname][0]
             ops.colsum(dY, lddy, M, O, self.grads[bias], dt=self.dt, ws=self.ws(ops.colsum_ws(M, O)))
         self._side_exit(h)
-
-    def _km_ok(self, O, C, KW, T, n_cols):
-        """conv weight gradients that take the K-major path (conv_mode 6): the FFN conv1
-        (k = 9) and PostNet (k = 5) weights.  tools/km_wgrad_bench.py, B = 32, GEMM + slice sum
-        + both transposes vs the MN-major implicit-conv GEMM: decoder conv1 464 -> 372 us,
-        encoder conv1 115 -> 110, PostNet 218 / 237 / 221 -> 125 / 98 / 75; the k = 3
-        predictor convs lose (58 -> 67: the transposes cost more than the GEMM saves)."""
-        return (self.dt == 1 and KW >= 5 and n_cols is None and
-                C % 8 == 0 and O % 8 == 0 and (KW - 1) // 2 < T)
 
     def _km_image(self, key, C, ld):
         """bf16 [C][ld] image with a zeroed guard of 64 elements before row 0 and after the
@@ -749,13 +582,8 @@ class FS2Engine:
         O, C, KW = self._wspecs[wname]
         P = (KW - 1) // 2
         B = M // T
-        Bt = B * (T + 2 * P)
-        ncol = KW * C
-        tiles = -(-O // 256) * -(-ncol // 256)
-        # one (split, tile) unit per CU; >= 16 K-tiles per unit, <= 25 fp32 slices to sum
-        cus = ctas if 0 < ctas < 256 else 256
-        S = max(1, min(cus // tiles, -(-Bt // 64) // 16, 25))
-        Kp = round_up(Bt, 64 * S)
+        p = lowering.wgrad_plan(O, C, KW, self.dt, M, T, lddy, ldx, None, ctas)
+        Kp, S, stride = p.K, p.ns, p.stride
         dYT = self._km_image("dy", O, Kp)
         XT = self._km_image("x", C, Kp)
         ws = self.ws(max(ops.pad_transpose_ws(Kp, O), 1))
@@ -774,16 +602,13 @@ class FS2Engine:
             ops.pad_transpose(dY, lddy, B, T, O, P, 0, dYT, Kp, Kp, dt=self.dt, colsum=colsum,
                               ws=ws, **bk)
         ops.pad_transpose(X, ldx, B, T, C, P, 1, XT, Kp, Kp, dt=self.dt, **bk)
-        stride = O * ncol
-        ws = self.ws(S * stride)
-        if gemm_tag:
-            self._tic(gemm_tag)
-        ops.gemm(O, ncol, Kp, dYT, Kp, XT, Kp, ws, ncol, dt=self.dt, conv=(6, T, KW, C),
+        ws = self.ws(p.ws_floats)
+        self._tic(gemm_tag)
+        ops.gemm(O, p.ldc, Kp, dYT, Kp, XT, Kp, ws, p.ldc, dt=self.dt, conv=(6, T, KW, C),
                  c_fp32=1, split_k=S, split_stride=stride if S > 1 else 0, max_ctas=ctas,
                  k_eff=keff)
-        if gemm_tag:
-            self._toc(gemm_tag)
-        ops.sum_slices(ws, S, stride, stride, self.grads[wname], accumulate=1)
+        self._toc(gemm_tag)
+        ops.sum_slices(ws, S, stride, stride, self.grads[wname], accumulate=p.accumulate)
         return True
 
     def _wgrad_impl(self, dY, lddy, X, ldx, M, T, wname, n_cols=None, gemm_tag=None, bias=None,
@@ -792,58 +617,30 @@ class FS2Engine:
         ``gemm_tag``: HIP events around the GEMM launch alone (bench.py's roofline entry for
         the FFN conv1 weight gradient), on the stream it runs on (the side stream)."""
         O, C, KW = self._wspecs[wname]
-        if self._km_ok(O, C, KW, T, n_cols) and lddy % 8 == 0 and ldx % 8 == 0:
+        if lowering.km_ok(O, C, KW, self.dt, T, n_cols, lddy, ldx):
             return self._wgrad_km(dY, lddy, X, ldx, M, T, wname, gemm_tag, bias, dy_img, ctas,
                                   grad_end)
         if dy_img is not None:
             raise RuntimeError(f"{wname}: a padded dY image needs the K-major weight gradient")
-        if n_cols is not None and n_cols != KW * C and KW == 1 and n_cols % 8 == 0 and self.dt == 1:
-            # padded X columns (concat_proj: 2D + 5 -> 776): split-K slices over the padded width,
-            # then the valid columns added into the gradient -- the unpadded GEMM's odd row
-            # pitch forced the scalar atomic epilogue (92 -> ~35 us, tools/wgrad1x1_bench.py)
-            K = round_up(M, self.epc)
-            ns = eff_split(K, wgrad_slices(O, n_cols, n_cols, K, self.dt), BK[self.dt])
-            ns = max(ns, 2)
-            stride = O * n_cols
-            ws = self.ws((ns + 1) * stride)
-            ops.gemm(O, n_cols, K, dY, lddy, X, ldx, ws, n_cols, dt=self.dt, a_kmajor=0,
-                     b_kmajor=0, c_fp32=1, kvalid=M, nvalid=n_cols, split_k=ns,
-                     split_stride=stride, max_ctas=ctas)
-            tot = ws[ns * stride:(ns + 1) * stride]
-            ops.sum_slices(ws, ns, stride, stride, tot, accumulate=0)
-            self.grads[wname].view(O, C).add_(tot.view(O, n_cols)[:, :C])
-            return
-        Ncols = n_cols or KW * C
-        K = round_up(M, self.epc)
-        tiles = -(-O // 128) * -(-Ncols // 128)
-        split = 1
-        if tiles < 256:
-            split = max(1, min(-(-_WG_ATOMIC_UNITS // tiles), K // (BK[self.dt] * 4)))
-        conv = (3, T, KW, C) if KW > 1 else None
-        ldc = C * KW
-        ns = wgrad_slices(O, Ncols, ldc, K, self.dt, _WG_SLICE_CU)
-        if ns == 1 and self.dt == 1 and Ncols == ldc and O * ldc > 600_000:
-            tiles = -(-O // 256) * -(-Ncols // 256)
-            ns = max(1, min(-(-_SLICE_TARGET // tiles), (K // 64) // 8))
-        ns = eff_split(K, ns, BK[self.dt])
-        if ns > 1:
-            # small outputs: split-K slices into fp32 planes, summed in a fixed order -- instead
-            # of tens of fp32 atomics landing on every output element
-            stride = O * ldc
-            ws = self.ws(ns * stride)
-            if gemm_tag:
-                self._tic(gemm_tag)
-            ops.gemm(O, Ncols, K, dY, lddy, X, ldx, ws, ldc, dt=self.dt, a_kmajor=0, b_kmajor=0,
-                     conv=conv, c_fp32=1, kvalid=M, nvalid=ldc, split_k=ns, split_stride=stride,
-                     max_ctas=ctas)
-            if gemm_tag:
-                self._toc(gemm_tag)
-            ops.sum_slices(ws, ns, stride, stride, self.grads[wname], accumulate=1)
-            return
-        # conv weight gradients land contiguous in the [O][KW][C] flat layout (model._kw_major)
-        ops.gemm(O, Ncols, K, dY, lddy, X, ldx, self.grads[wname], ldc, dt=self.dt, a_kmajor=0,
-                 b_kmajor=0, conv=conv, c_fp32=1, kvalid=M, nvalid=KW * C, accumulate=1,
-                 split_k=split, max_ctas=ctas)
+        p = lowering.wgrad_plan(O, C, KW, self.dt, M, T, lddy, ldx, n_cols, ctas)
+        ns, stride = p.ns, p.stride
+        # split-K fp32 atomics straight into the [O][KW][C] flat gradient, or ns fp32 slices
+        atomic = p.path == "atomic"
+        out = self.grads[wname] if atomic else self.ws(p.ws_floats)
+        tag = gemm_tag if p.path == "slices" else None
+        self._tic(tag)
+        ops.gemm(O, n_cols or KW * C, p.K, dY, lddy, X, ldx, out, p.ldc, dt=self.dt, a_kmajor=0,
+                 b_kmajor=0, conv=(3, T, KW, C) if KW > 1 else None, c_fp32=1, kvalid=M,
+                 nvalid=p.ldc, accumulate=int(atomic), split_k=ns, split_stride=stride,
+                 max_ctas=ctas)
+        self._toc(tag)
+        if p.path == "slices":
+            ops.sum_slices(out, ns, stride, stride, self.grads[wname], accumulate=p.accumulate)
+        elif p.path == "cols":
+            # padded X columns: summed into the plane after the slices, the valid ones added
+            tot = out[ns * stride:(ns + 1) * stride]
+            ops.sum_slices(out, ns, stride, stride, tot, accumulate=p.accumulate)
+            self.grads[wname].view(O, C).add_(tot.view(O, p.ldc)[:, :C])
 
     def _bias_grad(self, dY, lddy, M, n, gname):
         h = self._side_enter(dY)
@@ -879,7 +676,8 @@ class FS2Engine:
         # X1 (fs2_ln_fwd img).  Its 2P tail rows are read only by the dropped pad-row outputs of
         # the last utterance (c_row = (T, -2P); each output row sums its own 2P+1 image rows):
         # one image per shape, reused layer after layer, its tail zeroed once at allocation
-        img = self._fwd_image(B * (T + 2 * P1), 2 * P1, D) if self._pad_fwd(w1, M, T) else None
+        img = self._fwd_image(B * (T + 2 * P1), 2 * P1, D) if lowering.fwd_padded(
+            F, D, KW1, self.dt, M, T, self._okc[w1]) else None
         ops.ln_fwd(X, D, P[prefix + "norm1.norm.weight"], P[prefix + "norm1.norm.bias"], 1e-6, X1, D,
                    mean1, rstd1, M, D, dt=self.dt, seed=seed, r=Ao, ldr=D, p_r=p_drop, salt_r=s_r1,
                    s_out=s1, img=img, img_t=T, img_p=P1)
@@ -920,12 +718,12 @@ class FS2Engine:
                    dbeta=G[prefix + "norm2.norm.bias"], dcol=G[prefix + "pos_ffn.2.conv.bias"])
         w2 = prefix + "pos_ffn.2.conv.weight"
         w1 = prefix + "pos_ffn.0.conv.weight"
-        pad = self._pad_dgrad(w1)
-        if pad and not self._pad_dgrad_fits(w1, B, T):
-            # the weight images of this conv were built tap-reversed for the padded path
-            raise ValueError(f"{w1}: batch of {B} x {T} tokens exceeds the 32-bit offsets of the "
-                             "padded conv data gradient; split the batch")
-        if pad:   # conv2's data gradient lands in the zero-padded image conv1's reads
+        pad = self._okc[w1] & lowering.W_REV
+        if pad:   # conv2's data gradient lands in the zero-padded image conv1's reads, for which
+            # alone this conv's weight images were built
+            refusal = lowering.dgrad_refusal(*self._wspecs[w1], B, T)
+            if refusal:
+                raise ValueError(f"{w1}: {refusal}")
             P1 = (self._wspecs[w1][2] - 1) // 2
             img, dHc = self._dy_image(prefix, B, T, P1, F)
             crow = {"c_row": (T, 2 * P1)}

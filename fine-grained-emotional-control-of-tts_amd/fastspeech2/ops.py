@@ -13,8 +13,7 @@ import sys
 import torch
 
 from . import _native as N
-
-EPC = {N.F32: 4, N.BF16: 8}   # elements per 16-byte chunk (GEMM K / pitch granularity)
+from .lowering import EPC, round_up  # noqa: F401
 
 
 def _p(x):
@@ -32,10 +31,6 @@ def _s():
 def _chk(rc, name):
     if rc != 0:
         raise RuntimeError(f"{name} returned {rc}")
-
-
-def round_up(x, m):
-    return (x + m - 1) // m * m
 
 
 # FS2_GEMM_TRACE=1: count fs2_gemm calls by (shape, operand flags, kernel and grid from

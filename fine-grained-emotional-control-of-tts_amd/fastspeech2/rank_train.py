@@ -29,7 +29,7 @@ import torch.nn.functional as F
 from . import _native as N
 from . import ops
 from .attention import attention_bwd, attention_fwd, use_flash
-from .engine import BK, eff_split
+from .lowering import rank_slices
 from .intensity import RankModel, stage_mixup
 from .ops import round_up
 
@@ -109,20 +109,13 @@ class RankTrainEngine:
         ops.gemm(M, C, K, dY, lddy, Wb, K, out, ldo, dt=self.dt,
                  conv=(5, T, KW, O) if KW > 1 else None, **epi)
 
-    def _slices(self, O, ncols, K):
-        """split-K slice count of a weight gradient: about one (tile, slice) unit per CU, at
-        least four K-tiles per slice"""
-        bk = BK[self.dt]
-        tiles = -(-O // 128) * -(-ncols // 128)
-        return eff_split(K, max(1, min(256 // tiles, (K // bk) // 4)), bk)
-
     def _wgrad(self, dY, lddy, X, ldx, rows, O, ncols, out, conv=None):
         """out[O][ncols] (fp32, overwritten) = dY^T X over ``rows`` token rows, both operands
         MN-major; ``conv`` = (3, rows per utterance, KW, C): X taken tap by tap (a conv weight
         gradient over zero-padded images, columns n = (tap, channel)).  Split-K slices summed in
         a fixed order."""
         K = round_up(rows, self.epc)
-        ns = self._slices(O, ncols, K)
+        ns = rank_slices(O, ncols, K, self.dt)
         kw = dict(dt=self.dt, a_kmajor=0, b_kmajor=0, conv=conv, c_fp32=1, kvalid=rows)
         if ns > 1:
             stride = O * ncols

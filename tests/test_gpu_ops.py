@@ -628,7 +628,7 @@ def test_gemm_big_tile_paths_bf16(cuda, Bn, T):
             relu=1)
     assert rel(Y, out.detach().reshape(-1, O)) < 2e-2
     Mp = Bn * (T + 2 * P)
-    from fastspeech2.engine import dgrad_split
+    from fastspeech2.lowering import dgrad_split
     split = dgrad_split(Mp, Cin, KW * O, 1)
     Xpad = torch.empty(split, Mp, Cin, device=cuda)
     gemm_on(dgrad, Mp, Cin, KW * O, G, O, Wb, KW * O, Xpad, Cin, dt=1, conv=(4, T, KW, O), c_fp32=1,

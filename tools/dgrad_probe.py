@@ -24,27 +24,28 @@ def timed(fn, n=10):
 
 def case(name, B, T, O, C, KW):
     from fastspeech2 import ops
-    from fastspeech2.engine import dgrad_split
+    from fastspeech2.lowering import dgrad_split
     P = (KW - 1) // 2
     M = B * T
     Mp = B * (T + 2 * P)
     K = KW * O
+    split = dgrad_split(Mp, C, K, 1)
+    split_stride = Mp * C if split > 1 else 0
     bf = torch.bfloat16
     dY = (torch.randn(M, O, device="cuda") * 0.5).to(bf)
     Wb = (torch.randn(C, K, device="cuda") * 0.05).to(bf)
-    split = dgrad_split(Mp, C, K, 1)
     Xpad = torch.empty(split, Mp, C, dtype=torch.float32, device="cuda")
     fl = 2.0 * Mp * C * K
     img = torch.zeros(Mp + 2 * P + 8, O, device="cuda", dtype=bf)
 
     def a():
         ops.gemm(Mp, C, K, dY, O, Wb, K, Xpad, C, dt=1, conv=(4, T, KW, O), c_fp32=1,
-                 split_k=split, split_stride=Mp * C if split > 1 else 0)
+                 split_k=split, split_stride=split_stride)
     ta = timed(a)
 
     def b():
         ops.gemm(Mp, C, K, img, O, Wb, K, Xpad, C, dt=1, c_fp32=1, split_k=split,
-                 split_stride=Mp * C if split > 1 else 0)
+                 split_stride=split_stride)
     tb = timed(b)
     print(f"{name}: split {split}  conv_mode 4 {ta:7.1f} us ({fl / ta / 1e6:5.0f} TF/s)   "
           f"plain overlapping rows {tb:7.1f} us ({fl / tb / 1e6:5.0f} TF/s)", flush=True)

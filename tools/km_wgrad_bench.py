@@ -24,6 +24,7 @@ def timed(fn, n=10):
 
 def case(name, B, T, C, O, KW, splits):
     from fastspeech2 import ops
+    from fastspeech2.lowering import EPC
     P = (KW - 1) // 2
     M = B * T
     bf = torch.bfloat16
@@ -34,7 +35,7 @@ def case(name, B, T, C, O, KW, splits):
     stride = O * Ncols
     ws = torch.empty(8 * stride, device="cuda")
     out = torch.zeros(O, Ncols, device="cuda")
-    K = (M + 7) // 8 * 8
+    K = ops.round_up(M, EPC[1])
     ns = 3
 
     def a():

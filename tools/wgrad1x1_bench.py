@@ -9,7 +9,7 @@ os.environ.setdefault("FS2_HIP_LIB", os.path.join(ROOT, "fine-grained-emotional-
 sys.path.insert(0, os.path.join(ROOT, "fine-grained-emotional-control-of-tts_amd"))
 import torch  # noqa: E402
 from fastspeech2 import ops  # noqa: E402
-from fastspeech2.engine import wgrad_slices, eff_split  # noqa: E402
+from fastspeech2.lowering import eff_split, wgrad_plan  # noqa: E402
 
 
 def timed(fn, n=20):
@@ -41,26 +41,20 @@ def main():
         dY = (torch.randn(T, O, device="cuda") * 0.5).to(bf)
         X = (torch.randn(T, C, device="cuda") * 0.5).to(bf)
         ref = dY.float().t() @ X.float()
-        K = (T + 7) // 8 * 8
+        path, K, pns, ldc, st, _, _ = wgrad_plan(O, C, 1, 1, T, T, O, C, None, 0)
         G = torch.zeros(O, C, device="cuda")
         fl = 2.0 * T * O * C
         ws = torch.empty(64 * O * C, device="cuda")
 
-        def engine():
-            ns = eff_split(K, wgrad_slices(O, C, C, K, 1), 64)
-            if ns == 1 and O * C > 600_000:
-                ns = eff_split(K, max(1, min(-(-240 // (-(-O // 256) * -(-C // 256))), (K // 64) // 8)), 64)
-            if ns > 1:
-                st = O * C
+        def engine():     # the engine's plan for this shape: slices (+) or atomic split-K (-)
+            if path == "slices":
                 ops.gemm(O, C, K, dY, O, X, C, ws, C, dt=1, a_kmajor=0, b_kmajor=0, c_fp32=1,
-                         kvalid=T, nvalid=C, split_k=ns, split_stride=st)
-                ops.sum_slices(ws, ns, st, st, G, accumulate=1)
-                return ns
-            tiles = -(-O // 128) * -(-C // 128)
-            split = max(1, min(-(-512 // tiles), K // 256)) if tiles < 256 else 1
+                         kvalid=T, nvalid=C, split_k=pns, split_stride=st)
+                ops.sum_slices(ws, pns, st, st, G, accumulate=1)
+                return pns
             ops.gemm(O, C, K, dY, O, X, C, G, C, dt=1, a_kmajor=0, b_kmajor=0, c_fp32=1,
-                     kvalid=T, nvalid=C, accumulate=1, split_k=split)
-            return -split
+                     kvalid=T, nvalid=C, accumulate=1, split_k=pns)
+            return -pns
         G.zero_()
         how = engine()
         torch.cuda.synchronize()
