@@ -431,7 +431,12 @@ int fs2_intensity_head(const void* H, int64_t ldh, const float* emo_table,
                        const float* bc, int B, int T, int D, int E, float* I, int dtype,
                        void* stream);
 /* out[b,p,:] = sum of I[b, t, :] over phoneme p's frames [sum d[:p], sum d[:p+1]) (clipped to
- * T) / max(d[b,p], 1) for p < phon_len[b]; 0 otherwise (train.py:33-49). Tp <= 1024.        */
+ * T) / max(d[b,p], 1) for p < phon_len[b]; 0 otherwise (train.py:33-49). Tp <= 1024.
+ * The sum runs over t in ascending order in fp32 and is divided once.  When the durations of an
+ * utterance add up to more than T, frames from T on are not read (a phoneme that starts at or
+ * after T sums nothing and comes out as +0), and the divisor is still the full d[b,p].
+ * phon_len[b] is clamped to [0, Tp]; positions p >= phon_len[b] are written as +0.0, and
+ * durations there are not read.  Durations must be >= 0.  Tp > 1024 is FS2_EINVAL.         */
 int fs2_phoneme_average(const float* I, int T, int E, const int64_t* durations,
                         const int64_t* phon_len, int B, int Tp, float* out, void* stream);
 
@@ -556,12 +561,18 @@ int fs2_rank_collate(const float* store, const int64_t* emo_off, const int64_t* 
  * fastspeech2/inference.py:60-63,85).  Convs on fs2_gemm (conv_mode 1 + conv_dil, transposed
  * convs as 3-tap polyphase conv_mode 5, act 3 / 4 epilogues, residual epilogue).
  * ------------------------------------------------------------------------------------------ */
-/* mel (B, n_mels, T) fp32 -> X[B*(T+2 pad)][ldx] (dtype), pad replicated frames each side   */
+/* mel (B, n_mels, T) fp32 -> X[B*(T+2 pad)][ldx] (dtype), pad replicated frames each side:
+ * row t of an utterance holds frame min(max(t - pad, 0), T - 1), so pad may exceed T - 1 (every
+ * pad row repeats the first or the last frame; never a reflection).  Columns n_mels..ldx-1 are
+ * zeros.  FS2_EINVAL for ldx < n_mels, T < 1, pad < 0 or a null pointer.                     */
 int fs2_vocoder_input(const float* mel, int B, int n_mels, int T, int pad, void* X, int ldx,
                       int dtype, void* stream);
-/* y = leaky_relu(x, slope); n % (16 / sizeof(dtype)) == 0, 16-byte aligned                  */
+/* y = leaky_relu(x, slope) = x >= 0 ? x : x * slope in fp32 (-0.0 stays -0.0, NaN stays NaN);
+ * n % (16 / sizeof(dtype)) == 0, x and y 16-byte aligned, else FS2_EINVAL.  y may be x (in
+ * place): every element is read and written by the same thread.                            */
 int fs2_leaky_relu(const void* x, void* y, int64_t n, float slope, int dtype, void* stream);
-/* y = leaky_relu(((a + b) + c) / 3, slope)                                                  */
+/* y = leaky_relu(((a + b) + c) / 3, slope), each fp32 operation rounded once, in this order;
+ * the same size and alignment rules for a, b, c and y; y may be any of the inputs            */
 int fs2_mean3_leaky_relu(const void* a, const void* b, const void* c, void* y, int64_t n,
                          float slope, int dtype, void* stream);
 
@@ -569,6 +580,10 @@ int fs2_mean3_leaky_relu(const void* a, const void* b, const void* c, void* y, i
 int fs2_fill(void* X, int64_t n, float value, int dtype, void* stream);
 /* X[i] += alpha * Y[i] over n elements of dtype                                           */
 int fs2_add(void* X, const void* Y, int64_t n, float alpha, int dtype, void* stream);
+/* dst[i] = src[i] converted, for the four pairs of FS2_F32 / FS2_BF16 (fp32 -> bf16 rounds to
+ * nearest even, NaN stays NaN; equal dtypes copy); any other dtype on either side is
+ * FS2_EINVAL.  One element per thread: src and dst need only their element's own alignment,
+ * no 16-byte alignment and no multiple-of-vector n.  fs2_fill and fs2_add likewise.          */
 int fs2_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, void* stream);
 /* Dropout seed base (device-resident, added to every launch's seed argument): HIP-graph
  * replays of a step captured with seed 0 set it to the step's seed first; eager steps leave
