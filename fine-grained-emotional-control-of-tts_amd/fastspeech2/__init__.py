@@ -10,6 +10,12 @@ The rank model's data path (``emo_rank_tts/rank_model/dataset.py``):
 
     from fastspeech2 import FineGrainedDataset, RankGpuCollate, RankDeviceStore
 
+The FastSpeech2 data path with the set resident on the device (index-list batches, cached
+intensity input):
+
+    from fastspeech2 import FS2DeviceStore
+    from fastspeech2.train import train_one_epoch
+
 Compute runs only through libfs2_hip.so (include/fs2_hip.h); see DESIGN.md.
 """
 
@@ -20,7 +26,7 @@ import yaml
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 _RANK_DATASET = ("FineGrainedDataset", "RankGpuCollate", "RankDeviceStore")
-__all__ = ["load_config", *_RANK_DATASET]
+__all__ = ["load_config", *_RANK_DATASET, "FS2DeviceStore"]
 
 
 def __getattr__(name):
@@ -28,6 +34,9 @@ def __getattr__(name):
     if name in _RANK_DATASET:
         from . import rank_dataset
         return getattr(rank_dataset, name)
+    if name == "FS2DeviceStore":
+        from . import device_store
+        return device_store.FS2DeviceStore
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -177,6 +177,7 @@ SIGNATURES = {
     "fs2_collate_phonemes": (I, [P, P, P, P, I, I, P, P, P, P]),
     "fs2_collate_frames": (I, [P, P, P, P, P, I, I, I, P, P, P, P, P, P]),
     "fs2_rank_collate": (I, [P, P, P, P, P, I, I, I, P, P, P, P]),
+    "fs2_store_collate": (I, [P, P, P, P, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P]),
     "fs2_vocoder_input": (I, [P, I, I, I, I, P, I, I, P]),
     "fs2_leaky_relu": (I, [P, P, I64, Fl, I, P]),
     "fs2_mean3_leaky_relu": (I, [P, P, P, P, I64, Fl, I, P]),

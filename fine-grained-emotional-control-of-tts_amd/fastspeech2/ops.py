@@ -470,6 +470,14 @@ def rank_collate(store, emo_off, emo_len, neu_off, neu_len, B, T, C, emo_X, neu_
          "fs2_rank_collate")
 
 
+def store_collate(fstore, istore, desc, cache, B, Tp, Tm, n_mels, E, phon_out, dur_out, in_len,
+                  mel_out, pitch_out, energy_out, rank_x, out_len, intensity=None):
+    _chk(N.lib().fs2_store_collate(_p(fstore), _p(istore), _p(desc), _p(cache), B, Tp, Tm, n_mels,
+                                   E, _p(phon_out), _p(dur_out), _p(in_len), _p(mel_out),
+                                   _p(pitch_out), _p(energy_out), _p(rank_x), _p(out_len),
+                                   _p(intensity), _s()), "fs2_store_collate")
+
+
 def weight_prep_table(entries):
     """Device table of fs2_wprep_desc for fs2_weight_prep_batched.  entries: list of
     (W, O, C, KW, w_okc, Wf, ldf, Wb, ldb); returns (table tensor, n, total_tiles).  The tensors

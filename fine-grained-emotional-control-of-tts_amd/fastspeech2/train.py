@@ -17,6 +17,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
+from .intensity import get_intensity_representation
 from .loss import fused_loss
 from .optim import FusedAdamW
 
@@ -31,6 +32,40 @@ def train_step(model, criterion, optim, batch, intensity, epoch=0):
     loss["total_loss"].backward()
     optim.step()
     return predictions, loss
+
+
+def train_one_epoch(trainer, store, batch_size, extractor, shuffle=True, generator=None,
+                    drop_last=False, cached=True):
+    """The body of the reference's ``train_one_epoch`` (train.py:60-81) without logging, over a
+    ``FS2DeviceStore``: per batch the intensity input, then ``trainer.step``.  ``cached=True``
+    takes the intensity from ``store.collate(..., intensity=True)`` (the store's cache, which
+    ``store.cache_intensity(extractor)`` must have filled); ``cached=False`` runs
+    ``get_intensity_representation`` on every batch as the reference does.  The loss vectors
+    are summed on the device and copied back once: returns their mean over the epoch's steps
+    (the reference's ``epoch_avg_loss``) as a host tensor.  Under data parallelism (an
+    initialised ``torch.distributed``) each rank takes its share of ``epoch_order``; a shuffled
+    epoch then needs a ``generator`` seeded alike on every rank."""
+    rank, world = 0, 1
+    if dist.is_available() and dist.is_initialized():
+        rank, world = dist.get_rank(), dist.get_world_size()
+    if world > 1 and shuffle and generator is None:
+        raise ValueError("a shuffled epoch under data parallelism needs a generator seeded alike "
+                         "on every rank")
+    trainer.model.train()
+    total, steps = None, 0
+    for item in store.batches(batch_size, shuffle=shuffle, generator=generator,
+                              drop_last=drop_last, rank=rank, world_size=world,
+                              intensity=cached, extractor=extractor if cached else None):
+        if cached:
+            batch, intensity = item
+        else:
+            batch, intensity = item, get_intensity_representation(extractor, item)
+        loss = trainer.step(batch, intensity, mel_len_max=batch[3].shape[1])
+        total = loss.clone() if total is None else total.add_(loss)
+        steps += 1
+    if total is None:
+        raise ValueError("the epoch has no batch")
+    return (total / steps).cpu()
 
 
 class GradBucketer:

@@ -557,6 +557,29 @@ int fs2_rank_collate(const float* store, const int64_t* emo_off, const int64_t* 
                      float* emo_X, float* neu_X, int64_t* length, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The FastSpeech2 collate (fastspeech2/dataset.py:62-133) from a device-resident store
+ * (fastspeech2/device_store.py), one launch.  fstore: per utterance its (n_mels + 2, T_u)
+ * channel-major fp32 block cat(mel, pitch, energy), blocks back to back (bases 4-byte aligned
+ * only); istore: per utterance n_phon int64 phoneme ids, then n_phon durations.  desc is the
+ * batch's gathered descriptor table, (7, B) row-major int64, row b of the batch in column b:
+ * float offset, frames, int offset, phonemes, speaker, emotion, cache offset (offsets in
+ * elements; speaker and emotion are not read).  Outputs as fs2_collate_phonemes /
+ * fs2_collate_frames write them: phoneme / duration (B, Tp) int64 zero padded, input_lengths =
+ * phonemes, mel (B, Tm, n_mels) contiguous, pitch / energy (B, Tm), rank_x (B, n_mels + 2, Tm),
+ * output_lengths = frames; frames >= Tm and phonemes >= Tp are not written past Tm / Tp.  With
+ * cache != NULL also intensity (B, Tp, E) fp32: row b's cached (phonemes, E) block at cache +
+ * cache offset, zeros past it (all zeros for a negative cache offset).  No workspace, no atomics.
+ * Returns 0 without a launch when B*Tm == 0; FS2_EINVAL for a null pointer (cache and, without
+ * a cache, intensity may be null), B, Tp or Tm < 0, B > 65535, n_mels outside [1, 128], or a
+ * cache with E < 1.
+ * ------------------------------------------------------------------------------------------ */
+int fs2_store_collate(const float* fstore, const int64_t* istore, const int64_t* desc,
+                      const float* cache, int B, int Tp, int Tm, int n_mels, int E,
+                      int64_t* phoneme_padded, int64_t* duration_padded, int64_t* input_lengths,
+                      float* mel_padded, float* pitch_padded, float* energy_padded, float* rank_x,
+                      int64_t* output_lengths, float* intensity, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * HiFi-GAN generator forward (speechbrain HIFIGAN.decode_batch,
  * fastspeech2/inference.py:60-63,85).  Convs on fs2_gemm (conv_mode 1 + conv_dil, transposed
  * convs as 3-tap polyphase conv_mode 5, act 3 / 4 epilogues, residual epilogue).
