@@ -16,6 +16,10 @@ intensity input):
     from fastspeech2 import FS2DeviceStore
     from fastspeech2.train import train_one_epoch
 
+The log-mel front end (``emo_rank_tts/rank_model/audio_util.py::get_mel``), batched on the GPU:
+
+    from fastspeech2 import MelFrontEnd, get_mel
+
 Compute runs only through libfs2_hip.so (include/fs2_hip.h); see DESIGN.md.
 """
 
@@ -26,7 +30,8 @@ import yaml
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 _RANK_DATASET = ("FineGrainedDataset", "RankGpuCollate", "RankDeviceStore")
-__all__ = ["load_config", *_RANK_DATASET, "FS2DeviceStore"]
+_AUDIO = ("MelFrontEnd", "get_mel")
+__all__ = ["load_config", *_RANK_DATASET, "FS2DeviceStore", *_AUDIO]
 
 
 def __getattr__(name):
@@ -37,6 +42,9 @@ def __getattr__(name):
     if name == "FS2DeviceStore":
         from . import device_store
         return device_store.FS2DeviceStore
+    if name in _AUDIO:
+        from . import audio
+        return getattr(audio, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -25,7 +25,9 @@ Differences, each deliberate:
 * ``synthesize`` returns mel spectrograms; ``vocode`` then decodes them the way the reference
   does (inference.py:82-83: ``model(...)[0].permute(0, 2, 1)`` -> ``vocoder.decode_batch``) with
   the HIP HiFi-GAN generator of ``fastspeech2.vocoder`` (architecture only: the
-  speechbrain hub weights are not available offline).
+  speechbrain hub weights are not available offline, DESIGN.md section 7);
+* ``mel_of`` is the inverse direction of ``vocode`` (``fastspeech2.audio``): mel -> ``vocode``
+  -> ``mel_of`` is the round trip.
 """
 
 import numpy as np
@@ -121,3 +123,19 @@ def vocode(vocoder, mels, n_mels=80):
     wav = vocoder.decode_batch(batch)
     hop = wav.shape[-1] // (T + 2 * vocoder.hp["inference_padding"])
     return wav, [hop * int(m.shape[0]) for m in mels]
+
+
+@torch.no_grad()
+def mel_of(wav, valid_samples, front_end, compression=True):
+    """The inverse direction of ``vocode``: per-sentence mels of a padded waveform batch, in
+    ``synthesize``'s list form.  wav: (B, 1, S) or (B, S); valid_samples: the per-sentence
+    sample counts ``vocode`` returned; front_end: a ``fastspeech2.audio.MelFrontEnd``.  One
+    batched front-end call; sentence i's mel is cut to ``valid_samples[i] // hop_length``
+    frames -- the frames ``vocode`` was given, and the cut of preprocess.py:117 to
+    ``sum(durations)``: the front end itself yields one frame more.  Returns the list of
+    (T_i, n_mels) mels and the list of T_i.  Every sentence needs more than n_fft / 2 samples."""
+    wav = wav.reshape(wav.shape[0], -1)
+    mel, _, _ = front_end(wav, lengths=[int(n) for n in valid_samples], layout="btc",
+                          compression=compression)
+    lens = [int(n) // front_end.hop_length for n in valid_samples]
+    return [mel[i, :lens[i]] for i in range(len(lens))], lens

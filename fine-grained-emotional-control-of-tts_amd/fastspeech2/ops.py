@@ -530,6 +530,23 @@ def mean3_leaky_relu(a, b, c, y, n, slope, *, dt):
          "fs2_mean3_leaky_relu")
 
 
+MELSPEC_FRAMES = 8   # frames per fs2_melspec workgroup (csrc/audio.hip MEL_F)
+
+
+def melspec(wav, offsets, B, window, twiddle, bands, band_w, n_fft, win_length, hop, n_mels,
+            T_max, layout_bct, compression, mel, energy, mel_len):
+    """bands: (n_mels, 2) int32 numpy array on the HOST (first bin, bins); the rest on the device"""
+    _chk(N.lib().fs2_melspec(_p(wav), _p(offsets), B, _p(window), _p(twiddle), bands.ctypes.data,
+                             _p(band_w), n_fft, win_length, hop, n_mels, T_max, int(layout_bct),
+                             int(compression), _p(mel), _p(energy), _p(mel_len), _s()),
+         "fs2_melspec")
+
+
+def energy_minmax(energy, mel_len, B, T_max, out):
+    _chk(N.lib().fs2_energy_minmax(_p(energy), _p(mel_len), B, T_max, _p(out), _s()),
+         "fs2_energy_minmax")
+
+
 def fill(X, n, value, *, dt):
     _chk(N.lib().fs2_fill(_p(X), n, value, dt, _s()), "fs2_fill")
 

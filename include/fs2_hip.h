@@ -599,6 +599,47 @@ int fs2_leaky_relu(const void* x, void* y, int64_t n, float slope, int dtype, vo
 int fs2_mean3_leaky_relu(const void* a, const void* b, const void* c, void* y, int64_t n,
                          float slope, int dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Log-mel front end (rank_model/audio_util.py:23-40 get_mel: speechbrain mel_spectogram with
+ * power 1, slaney filterbank, L2 energy, log compression, min-max energy normalisation;
+ * fastspeech2/audio.py builds the tables and restates the reference).  fp32 in and out.
+ *
+ * fs2_melspec: wav is the batch's waveforms packed back to back, utterance b the samples
+ * [offsets[b], offsets[b+1]) (offsets: B + 1 int64 on the device; 4-byte alignment only), L_b of
+ * them.  Frame t of an utterance is the n_fft samples from t * hop - n_fft / 2, reflected once at
+ * either end (torch.stft center=True, pad_mode="reflect"), times window; T_b = 1 + L_b / hop
+ * frames.  The reflection needs L_b > n_fft / 2: the lengths are on the device, so the caller
+ * checks that; the kernel clamps the reflected index into the utterance, so a shorter one gives
+ * other values but never a read outside its own samples (L_b == 0 reads nothing: zeros).
+ * Tables, all fp32 on the device except bands: window (n_fft, the hann window already
+ * zero-padded centred from win_length), twiddle (n_fft / 2 pairs cos, sin of 2 pi j / n_fft),
+ * band_w (the filters' weights back to back: filter m's bins bands[2m] .. bands[2m] +
+ * bands[2m+1] - 1).  bands is HOST memory, n_mels pairs (first bin, bins) of int32, read and
+ * validated before the call returns; a filter with no bins is (0, 0).  The device evaluates no
+ * transcendental but the final log.
+ *   mel[m] = sum over the filter's bins of band_w * |X|; with compression log of max(mel, 1e-5)
+ *   energy = sqrt of the sum of mel^2 over the filters, before compression
+ * Outputs: mel (B, T_max, n_mels) when layout_bct == 0, (B, n_mels, T_max) otherwise; energy
+ * (B, T_max); rows t >= T_b of both are exact zeros; mel_len[b] = T_b int64 (not clamped to
+ * T_max; frames >= T_max are not written).  One launch, no workspace, no atomics; a workgroup
+ * takes 8 consecutive frames of one utterance.  Returns 0 without a launch when B == 0;
+ * FS2_EINVAL, before any launch, for n_fft not a power of two or outside [64, 2048], win_length
+ * outside [1, n_fft], hop < 1, n_mels outside [1, 256], T_max < 1, B < 0 or B > 65535, a null
+ * pointer, or a filter with a negative entry or running past n_fft / 2 + 1 bins.
+ *
+ * fs2_energy_minmax: out[b][t] = (e[b][t] - min) / (max - min) for t < min(mel_len[b], T_max),
+ * min and max over those frames of utterance b (fp32; NaN when one of them is NaN), one IEEE
+ * subtraction and division per frame: 0 / 0 = NaN for a single frame or constant energy, the
+ * reference's value; 0 for the padded frames.  energy and out are (B, T_max); out may be energy
+ * (in place).  FS2_EINVAL for a null pointer, T_max < 1 or B < 0; 0 without a launch for B == 0.
+ * ------------------------------------------------------------------------------------------ */
+int fs2_melspec(const float* wav, const int64_t* offsets, int B, const float* window,
+                const float* twiddle, const int32_t* bands, const float* band_w, int n_fft,
+                int win_length, int hop, int n_mels, int T_max, int layout_bct, int compression,
+                float* mel, float* energy, int64_t* mel_len, void* stream);
+int fs2_energy_minmax(const float* energy, const int64_t* mel_len, int B, int T_max, float* out,
+                      void* stream);
+
 /* utilities */
 int fs2_fill(void* X, int64_t n, float value, int dtype, void* stream);
 /* X[i] += alpha * Y[i] over n elements of dtype                                           */
