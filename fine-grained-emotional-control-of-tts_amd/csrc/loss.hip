@@ -11,6 +11,10 @@
 //    divided by the tie count (torch amax/amin semantics).
 // All reductions are fp32 and deterministic (fixed-order block sums, no float atomics
 // except the two per-utterance SSIM normalisation sums).
+//
+// fs2_loss_fwd is the same pass without the gradient: mse_kernel and ssim_map_kernel take a
+// bool G (gradients wanted); with G = false the gradient stores, the dmap planes and the two
+// gradient kernels are compiled out, so no float atomic is left and the values are reproducible.
 #include "fs2_launch.h"
 
 namespace {
@@ -82,8 +86,8 @@ __constant__ float GAUSS1[WIN] = {0.00102838012f, 0.00759875821f, 0.0360007733f,
                                   0.0360007733f,  0.00759875821f, 0.00102838012f};
 __device__ __forceinline__ float gauss1(int i) { return GAUSS1[i]; }
 
-// ---- 1: MSE terms + their gradients -------------------------------------------------------
-template <typename T>
+// ---- 1: MSE terms + their gradients (G) ---------------------------------------------------
+template <typename T, bool G>
 __global__ void __launch_bounds__(256) mse_kernel(LossP p) {
   __shared__ float sh[8];
   const int b = blockIdx.x, B = p.B, Tm = p.Tm, Tp = p.Tp, NM = p.NM;
@@ -111,11 +115,15 @@ __global__ void __launch_bounds__(256) mse_kernel(LossP p) {
       for (int e = 0; e < V; ++e) {
         const float d1 = a[e] - y[e], d2 = c[e] - y[e];
         if (valid) { s_mel += d1 * d1; s_post += d2 * d2; }
-        g1[e] = valid ? cm * d1 : 0.f;
-        g2[e] = valid ? cp * d2 : 0.f;
+        if constexpr (G) {
+          g1[e] = valid ? cm * d1 : 0.f;
+          g2[e] = valid ? cp * d2 : 0.f;
+        }
       }
-      vstore<T>(dmo + i, g1);
-      vstore<T>(dpo + i, g2);
+      if constexpr (G) {
+        vstore<T>(dmo + i, g1);
+        vstore<T>(dpo + i, g2);
+      }
     }
   } else {
     for (int i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
@@ -123,8 +131,10 @@ __global__ void __launch_bounds__(256) mse_kernel(LossP p) {
       const float y = mt[i];
       const float d1 = to_f(mo[i]) - y, d2 = to_f(po[i]) - y;
       if (valid) { s_mel += d1 * d1; s_post += d2 * d2; }
-      dmo[i] = from_f<T>(valid ? cm * d1 : 0.f);
-      dpo[i] = from_f<T>(valid ? cp * d2 : 0.f);
+      if constexpr (G) {
+        dmo[i] = from_f<T>(valid ? cm * d1 : 0.f);
+        dpo[i] = from_f<T>(valid ? cp * d2 : 0.f);
+      }
     }
   }
   s_mel = block_sum(s_mel, sh);
@@ -153,9 +163,11 @@ __global__ void __launch_bounds__(256) mse_kernel(LossP p) {
     const bool vd = i < Pl, vn = i < Ln;
     if (vd) s_dur += e1 * e1;
     if (vn) { s_pi += e2 * e2; s_en += e3 * e3; }
-    dd[i] = from_f<T>(vd ? cd * e1 : 0.f);
-    dpi[i] = from_f<T>(vn ? cpi * e2 : 0.f);
-    den[i] = from_f<T>(vn ? ce * e3 : 0.f);
+    if constexpr (G) {
+      dd[i] = from_f<T>(vd ? cd * e1 : 0.f);
+      dpi[i] = from_f<T>(vn ? cpi * e2 : 0.f);
+      den[i] = from_f<T>(vn ? ce * e3 : 0.f);
+    }
   }
   s_dur = block_sum(s_dur, sh);
   s_pi = block_sum(s_pi, sh);
@@ -263,14 +275,14 @@ struct Walk {
   }
 };
 
-// ---- 3: SSIM map and its partial derivatives wrt the prediction's local statistics --------
+// ---- 3: SSIM map and (G) its partial derivatives wrt the prediction's local statistics ----
 // Separable Gaussian: a block takes SSIM_TI output rows of one utterance, stages the
 // normalised X / Y of the SSIM_TI + 10 input rows in LDS, filters along the mel axis (5 moment
 // planes), then along time -- 2 x 11 taps per moment instead of 121.
 constexpr int SSIM_TI = 16;
 constexpr int SSIM_MAXW = 96;                  // n_mels <= 96
 constexpr int SSIM_R = SSIM_TI + WIN - 1;
-template <typename T>
+template <typename T, bool G>
 __global__ void __launch_bounds__(256) ssim_map_kernel(LossP p) {
   __shared__ float sh[8];
   __shared__ float w1[WIN];
@@ -320,16 +332,18 @@ __global__ void __launch_bounds__(256) ssim_map_kernel(LossP p) {
     const float N2 = 2.f * sxy + C2, D2 = sxx + syy + C2;
     const float cs = N2 / D2, lum = L1 / D1;
     ss += lum * cs;
-    // d(cs)/d(syy) = -cs / D2 and d(cs)/d(sxy) = 2 / D2 share q = lum / D2: where prediction
-    // and target agree (cs = 1) the two planes are exactly -q and 2 q and cancel in
-    // ssim_grad_kernel term by term, as they do in autograd; -N2 / D2^2 did not
-    const float q = lum / D2;
-    const float dl_db = 2.f * (a - bb * lum) / D1;
-    const float Db = cs * dl_db + 2.f * q * (bb * cs - a);
-    const float Deyy = -cs * q;
-    const float Dexy = 2.f * q;
-    const long o = (long)b * p.npix + (long)i * OW + j;
-    p.dmap[o] = Db; p.dmap[plane + o] = Deyy; p.dmap[2 * plane + o] = Dexy;
+    if constexpr (G) {
+      // d(cs)/d(syy) = -cs / D2 and d(cs)/d(sxy) = 2 / D2 share q = lum / D2: where prediction
+      // and target agree (cs = 1) the two planes are exactly -q and 2 q and cancel in
+      // ssim_grad_kernel term by term, as they do in autograd; -N2 / D2^2 did not
+      const float q = lum / D2;
+      const float dl_db = 2.f * (a - bb * lum) / D1;
+      const float Db = cs * dl_db + 2.f * q * (bb * cs - a);
+      const float Deyy = -cs * q;
+      const float Dexy = 2.f * q;
+      const long o = (long)b * p.npix + (long)i * OW + j;
+      p.dmap[o] = Db; p.dmap[plane + o] = Deyy; p.dmap[2 * plane + o] = Dexy;
+    }
   }
   ss = block_sum(ss, sh);
   if (threadIdx.x == 0) p.ssim_part[(long)b * p.nblk_pix + blockIdx.x] = ss;
@@ -493,22 +507,25 @@ __global__ void ssim_apply_kernel(LossP p) {
   *d = from_f<T>(to_f(*d) + g);
 }
 
-template <typename T>
+template <typename T, bool G>
 int run_loss(LossP& p, hipStream_t s) {
-  hipLaunchKernelGGL(mse_kernel<T>, dim3(p.B, p.nch), dim3(256), 0, s, p);
+  hipLaunchKernelGGL((mse_kernel<T, G>), dim3(p.B, p.nch), dim3(256), 0, s, p);
   hipLaunchKernelGGL(minmax_part_kernel<T>, dim3(MMCH, p.B), dim3(256), 0, s, p);
   hipLaunchKernelGGL(minmax_count_kernel<T>, dim3(MMCH, p.B), dim3(256), 0, s, p);
-  hipLaunchKernelGGL(ssim_map_kernel<T>, dim3(p.nblk_pix, p.B), dim3(256), 0, s, p);
+  hipLaunchKernelGGL((ssim_map_kernel<T, G>), dim3(p.nblk_pix, p.B), dim3(256), 0, s, p);
   hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, s, p);
-  const unsigned nq = (unsigned)(((long)p.Tm * p.NM + 255) / 256);
-  hipLaunchKernelGGL(ssim_grad_kernel<T>, dim3((p.Tm + SSIM_TI - 1) / SSIM_TI, p.B), dim3(256),
-                     0, s, p);
-  hipLaunchKernelGGL(ssim_apply_kernel<T>, dim3(nq, p.B), dim3(256), 0, s, p);
+  if constexpr (G) {
+    const unsigned nq = (unsigned)(((long)p.Tm * p.NM + 255) / 256);
+    hipLaunchKernelGGL(ssim_grad_kernel<T>, dim3((p.Tm + SSIM_TI - 1) / SSIM_TI, p.B),
+                       dim3(256), 0, s, p);
+    hipLaunchKernelGGL(ssim_apply_kernel<T>, dim3(nq, p.B), dim3(256), 0, s, p);
+  }
   FS2_CHECK_LAUNCH();
   return 0;
 }
 
-void carve(LossP& p, float* ws) {
+// with_grads = false: the same layout up to ssim_part; dmap and dnmap do not exist
+void carve(LossP& p, float* ws, bool with_grads) {
   const int B = p.B;
   p.npix = (p.Tm - (WIN - 1)) * (p.NM - (WIN - 1));
   p.nblk_pix = (p.Tm - (WIN - 1) + SSIM_TI - 1) / SSIM_TI;   // ssim_map blocks per utterance
@@ -521,32 +538,30 @@ void carve(LossP& p, float* ws) {
   p.cnt_part = w; w += 2L * B * MMCH;
   p.scal = w; w += 4;
   p.ssim_part = w; w += (long)B * p.nblk_pix;
+  p.dmap = nullptr;
+  p.dnmap = nullptr;
+  if (!with_grads) return;
   w = (float*)(((uintptr_t)w + 15) & ~(uintptr_t)15);
   p.dmap = w; w += 3L * B * p.npix;
   p.dnmap = w;
 }
 
-}  // namespace
-
-extern "C" int64_t fs2_loss_workspace_floats(int B, int Tm, int NM) {
-  const long npix = (long)(Tm - (WIN - 1)) * (NM - (WIN - 1));
+// floats of every region up to ssim_part, plus one 16-byte unit of alignment slack
+long small_regions(int B, int Tm, int NM) {
   const long nblk = (Tm - (WIN - 1) + SSIM_TI - 1) / SSIM_TI;
   const long nch = ((long)Tm * NM + LOSS_CHUNK - 1) / LOSS_CHUNK;
-  return 5L * B + 2L * B * nch + 8L * B + 6L * B * MMCH + 4 + B * nblk + 4 + 3L * B * npix +
-         (long)B * Tm * NM;
+  return 5L * B + 2L * B * nch + 8L * B + 6L * B * MMCH + 4 + B * nblk + 4;
 }
 
-extern "C" int fs2_loss_fwd_bwd(const fs2_loss_desc* d, void* stream) {
-  if (!d) return FS2_EINVAL;
-  if (d->B <= 0) return 0;
+// shape and pointer checks shared by both entries, then the LossP without the gradient pointers
+int fill(LossP& p, const fs2_loss_desc* d) {
   if (d->Tm < WIN || d->NM < WIN) return FS2_EINVAL;  // SSIM: kernel larger than input
   if (d->NM > SSIM_MAXW) return FS2_EINVAL;           // SSIM LDS tiles
+  if (d->dtype != FS2_BF16 && d->dtype != FS2_F32) return FS2_EINVAL;
   if (!d->mel_out || !d->postnet_out || !d->log_dur || !d->pitch_pred || !d->energy_pred ||
       !d->mel_tgt || !d->dur_tgt || !d->pitch_avg || !d->energy_avg || !d->mel_len ||
-      !d->phon_len || !d->loss_out || !d->d_mel_out || !d->d_postnet_out || !d->d_log_dur ||
-      !d->d_pitch || !d->d_energy || !d->workspace)
+      !d->phon_len || !d->loss_out || !d->workspace)
     return FS2_EINVAL;
-  LossP p{};
   p.B = d->B; p.Tm = d->Tm; p.Tp = d->Tp; p.NM = d->NM;
   p.mel_out = d->mel_out; p.post_out = d->postnet_out; p.log_dur = d->log_dur;
   p.pitch_pred = d->pitch_pred; p.energy_pred = d->energy_pred; p.mel_tgt = d->mel_tgt;
@@ -554,13 +569,44 @@ extern "C" int fs2_loss_fwd_bwd(const fs2_loss_desc* d, void* stream) {
   p.mel_len = d->mel_len; p.phon_len = d->phon_len;
   p.w_ssim = d->w_ssim; p.w_mel = d->w_mel; p.w_post = d->w_post; p.w_dur = d->w_dur;
   p.w_pitch = d->w_pitch; p.w_energy = d->w_energy;
-  p.loss_out = d->loss_out; p.d_mel = d->d_mel_out; p.d_post = d->d_postnet_out;
+  p.loss_out = d->loss_out;
+  p.vec = aligned16(p.mel_out) && aligned16(p.post_out) && aligned16(p.mel_tgt);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int64_t fs2_loss_workspace_floats(int B, int Tm, int NM) {
+  const long npix = (long)(Tm - (WIN - 1)) * (NM - (WIN - 1));
+  return small_regions(B, Tm, NM) + 3L * B * npix + (long)B * Tm * NM;
+}
+
+extern "C" int64_t fs2_loss_fwd_workspace_floats(int B, int Tm, int NM) {
+  return small_regions(B, Tm, NM);
+}
+
+extern "C" int fs2_loss_fwd_bwd(const fs2_loss_desc* d, void* stream) {
+  if (!d) return FS2_EINVAL;
+  if (d->B <= 0) return 0;
+  LossP p{};
+  if (int rc = fill(p, d)) return rc;
+  if (!d->d_mel_out || !d->d_postnet_out || !d->d_log_dur || !d->d_pitch || !d->d_energy)
+    return FS2_EINVAL;
+  p.d_mel = d->d_mel_out; p.d_post = d->d_postnet_out;
   p.d_dur = d->d_log_dur; p.d_pitch = d->d_pitch; p.d_energy = d->d_energy;
-  carve(p, d->workspace);
-  p.vec = aligned16(p.mel_out) && aligned16(p.post_out) && aligned16(p.mel_tgt) &&
-          aligned16(p.d_mel) && aligned16(p.d_post);
+  carve(p, d->workspace, true);
+  p.vec = p.vec && aligned16(p.d_mel) && aligned16(p.d_post);
   hipStream_t s = (hipStream_t)stream;
-  if (d->dtype == FS2_BF16) return run_loss<bf16>(p, s);
-  if (d->dtype == FS2_F32) return run_loss<float>(p, s);
-  return FS2_EINVAL;
+  return d->dtype == FS2_BF16 ? run_loss<bf16, true>(p, s) : run_loss<float, true>(p, s);
+}
+
+// Values only: the five d_* pointers of the descriptor are ignored (may be null)
+extern "C" int fs2_loss_fwd(const fs2_loss_desc* d, void* stream) {
+  if (!d) return FS2_EINVAL;
+  if (d->B <= 0) return 0;
+  LossP p{};
+  if (int rc = fill(p, d)) return rc;
+  carve(p, d->workspace, false);
+  hipStream_t s = (hipStream_t)stream;
+  return d->dtype == FS2_BF16 ? run_loss<bf16, false>(p, s) : run_loss<float, false>(p, s);
 }

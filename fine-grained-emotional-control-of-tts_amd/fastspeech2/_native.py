@@ -156,6 +156,8 @@ SIGNATURES = {
     "fs2_lr_scatter": (I, [P, P, P, I, I, I, I, P, I, P]),
     "fs2_loss_fwd_bwd": (I, [ctypes.POINTER(LossDesc), P]),
     "fs2_loss_workspace_floats": (I64, [I, I, I]),
+    "fs2_loss_fwd": (I, [ctypes.POINTER(LossDesc), P]),
+    "fs2_loss_fwd_workspace_floats": (I64, [I, I, I]),
     "fs2_adamw": (I, [P, P, P, P, I64, Fl, Fl, Fl, Fl, Fl, Fl, Fl, Fl, P]),
     "fs2_weight_prep": (I, [P, I, I, I, I, P, I, P, I, I, P]),
     "fs2_weight_prep_batched": (I, [P, I, I, I, P]),

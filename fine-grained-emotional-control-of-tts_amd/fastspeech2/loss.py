@@ -6,7 +6,9 @@ seven scalars as the reference (loss.py:176-186).  Forward and the gradient of
 terms, log1p duration targets, the [:mel_len]-on-phoneme-axis pitch/energy slicing, SB
 SSIM with masked min-max normalisation and [0,1] clamp); ``backward`` only scales the
 stored gradients by the upstream gradient.  Only ``total_loss`` is differentiable, which is
-what the reference train step uses (train.py:80).
+what the reference train step uses (train.py:80).  Validation needs no gradient:
+``eval_loss`` (and ``fused_loss(need_grads=False)``) run ``fs2_loss_fwd``, the same values
+without the gradient work.
 """
 
 import torch
@@ -21,7 +23,9 @@ LOSS_KEYS = ("total_loss", "ssim_loss", "mel_loss", "postnet_mel_loss", "dur_los
 
 def fused_loss(mel_out, postnet_out, log_dur, pitch_pred, energy_pred, mel_tgt, dur_tgt,
                pitch_avg, energy_avg, mel_len, phon_len, weights, need_grads=True):
-    """Run fs2_loss_fwd_bwd.  Returns (loss_vec[8] fp32 device tensor, grads tuple)."""
+    """Run fs2_loss_fwd_bwd.  Returns (loss_vec[8] fp32 device tensor, grads tuple).
+    ``need_grads=False`` runs fs2_loss_fwd instead: the same eight floats, ``None`` for the
+    gradients, no gradient tensor and only the small workspace allocated."""
     B, Tm, NM = mel_out.shape
     Tp = log_dur.shape[1]
     dt = N.dtype_code(mel_out.dtype)
@@ -46,18 +50,38 @@ def fused_loss(mel_out, postnet_out, log_dur, pitch_pred, energy_pred, mel_tgt, 
     d.mel_len, d.phon_len = c(mel_len, torch.int64), c(phon_len, torch.int64)
     (d.w_ssim, d.w_mel, d.w_post, d.w_dur, d.w_pitch, d.w_energy) = weights
     loss = torch.empty(8, dtype=torch.float32, device=dev)
+    d.loss_out = loss.data_ptr()
+    if not need_grads:
+        ws = torch.empty(int(ops.loss_fwd_ws(B, Tm, NM)), dtype=torch.float32, device=dev)
+        d.workspace = ws.data_ptr()
+        ops.loss_fwd(d)
+        return loss, None
     g_mel = torch.empty_like(mel_out)
     g_post = torch.empty_like(mel_out)
     g_dur = torch.empty(B, Tp, dtype=mel_out.dtype, device=dev)
     g_pitch = torch.empty(B, Tp, dtype=mel_out.dtype, device=dev)
     g_energy = torch.empty(B, Tp, dtype=mel_out.dtype, device=dev)
     ws = torch.empty(int(ops.loss_ws(B, Tm, NM)), dtype=torch.float32, device=dev)
-    d.loss_out = loss.data_ptr()
     d.d_mel_out, d.d_postnet_out = g_mel.data_ptr(), g_post.data_ptr()
     d.d_log_dur, d.d_pitch, d.d_energy = g_dur.data_ptr(), g_pitch.data_ptr(), g_energy.data_ptr()
     d.workspace = ws.data_ptr()
     ops.loss_fwd_bwd(d)
     return loss, (g_mel, g_post, g_dur, g_pitch, g_energy)
+
+
+def eval_loss(predictions, targets, weights):
+    """The seven ``LOSS_KEYS`` scalars of ``Loss.forward`` without any gradient (validation):
+    ``predictions`` and ``targets`` are the reference's 8-tuple and 6-tuple, ``weights`` is
+    ``Loss.weights``.  Nothing returned is differentiable."""
+    mel_target, target_durations, _, _, mel_length, phon_len = targets
+    (mel_out, postnet_mel_out, log_durations, predicted_pitch, average_pitch,
+     predicted_energy, average_energy, _) = predictions
+    with torch.no_grad():
+        loss, _ = fused_loss(mel_out, postnet_mel_out, log_durations, predicted_pitch.squeeze(-1),
+                             predicted_energy.squeeze(-1), mel_target, target_durations,
+                             average_pitch.squeeze(-1), average_energy.squeeze(-1), mel_length,
+                             phon_len, weights, need_grads=False)
+    return {k: loss[i] for i, k in enumerate(LOSS_KEYS)}
 
 
 class _LossFunction(torch.autograd.Function):

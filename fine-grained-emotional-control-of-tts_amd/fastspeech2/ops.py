@@ -368,6 +368,15 @@ def loss_ws(B, Tm, NM):
     return N.lib().fs2_loss_workspace_floats(B, Tm, NM)
 
 
+def loss_fwd(desc):
+    """The loss values alone; the descriptor's gradient pointers are ignored."""
+    _chk(N.lib().fs2_loss_fwd(ctypes.byref(desc), _s()), "fs2_loss_fwd")
+
+
+def loss_fwd_ws(B, Tm, NM):
+    return N.lib().fs2_loss_fwd_workspace_floats(B, Tm, NM)
+
+
 def adamw(param, grad, m, v, n, decay_mul, omb1, beta2, omb2, step_size, bc2_sqrt, eps, gscale):
     _chk(N.lib().fs2_adamw(_p(param), _p(grad), _p(m), _p(v), n, decay_mul, omb1, beta2, omb2,
                            step_size, bc2_sqrt, eps, gscale, _s()), "fs2_adamw")

@@ -9,6 +9,10 @@
   of the decoder / mel-linear / PostNet parameters runs on the aux stream during the encoder
   backward (one process: right after the decoder; DP: once their buckets are reduced), the
   rest after the backward (DP: after the last bucket).  One process per GPU, ``torch.distributed`` with the nccl (= RCCL) backend.
+* ``valid_one_epoch`` (train.py:112-165) and ``fit`` (train.py:244-264) are the other half of
+  the reference's ``train()``: the validation mean over ``FusedTrainer.eval_step`` (eval-mode
+  forward + the forward-only loss ``fs2_loss_fwd``), and the epoch loop with early stopping,
+  ``last_model.pth`` / ``best_model.pth`` and ``max_iterations``.
 """
 
 import os
@@ -17,6 +21,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
+from .device_store import epoch_order
 from .intensity import get_intensity_representation
 from .loss import fused_loss
 from .optim import FusedAdamW
@@ -66,6 +71,110 @@ def train_one_epoch(trainer, store, batch_size, extractor, shuffle=True, generat
     if total is None:
         raise ValueError("the epoch has no batch")
     return (total / steps).cpu()
+
+
+def _rank_world():
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank(), dist.get_world_size()
+    return 0, 1
+
+
+def valid_one_epoch(trainer, store, batch_size, extractor, cached=True, on_first_batch=None):
+    """The reference's ``valid_one_epoch`` (train.py:112-165) without logging, over a
+    ``FS2DeviceStore``: the store's order, the short last batch kept, per batch the intensity
+    input (as in ``train_one_epoch``) and ``trainer.eval_step``.  The model is in ``eval()`` for
+    the epoch and gets its previous mode back afterwards, also when a step raises.  The loss
+    vectors are summed on the device and copied back once; returns the sum divided by the
+    number of batches (every batch weighs the same, the reference's ``/ len(dataloader)``) as a
+    host tensor.  Under data parallelism each rank takes its share of ``epoch_order`` and the
+    sum and the batch count are all-reduced before the division, so every rank returns the same
+    vector.  ``on_first_batch(predictions, batch)`` is called once with the first batch's
+    8-tuple of predictions: the place for the reference's sample synthesis and plots."""
+    rank, world = _rank_world()
+    model = trainer.model
+    was_training = model.training
+    model.eval()
+    total, steps = None, 0
+    try:
+        for item in store.batches(batch_size, shuffle=False, drop_last=False, rank=rank,
+                                  world_size=world, intensity=cached,
+                                  extractor=extractor if cached else None):
+            if cached:
+                batch, intensity = item
+            else:
+                batch, intensity = item, get_intensity_representation(extractor, item)
+            mlm = batch[3].shape[1]
+            if steps == 0 and on_first_batch is not None:
+                loss, predictions = trainer.eval_step(batch, intensity, mel_len_max=mlm,
+                                                      return_predictions=True)
+                on_first_batch(predictions, batch)
+                del predictions
+            else:
+                loss = trainer.eval_step(batch, intensity, mel_len_max=mlm)
+            total = loss.clone() if total is None else total.add_(loss)
+            steps += 1
+    finally:
+        model.train(was_training)
+    if total is None:         # epoch_order gives every rank the same count: all ranks raise alike
+        raise ValueError("the epoch has no batch")
+    if world == 1:
+        return (total / steps).cpu()
+    count = torch.tensor([steps], dtype=torch.int64, device=total.device)
+    dist.all_reduce(total, op=dist.ReduceOp.SUM)
+    dist.all_reduce(count, op=dist.ReduceOp.SUM)
+    return (total / count.to(total.dtype)).cpu()
+
+
+def fit(trainer, train_store, valid_store, batch_size, extractor, n_epochs, patience,
+        max_iterations, exp_path=None, generator=None, cached=True, on_epoch=None):
+    """The reference's epoch loop (train.py:244-264).  Per epoch: ``train_one_epoch`` with the
+    reference loader's flags (shuffled, last short batch dropped), ``last_model.pth`` (:107),
+    ``valid_one_epoch``; ``val < best`` (a NaN never improves) resets the patience count and
+    writes ``best_model.pth``, anything else increments it and stops the loop at ``patience``;
+    then the global step grows by the epoch's train batches and the loop stops at
+    ``max_iterations``.  Checkpoints are ``torch.save(model.state_dict())`` into ``exp_path``
+    (``inference.load_model`` reads them), written by rank 0 only; without ``exp_path`` nothing
+    is written.  ``on_epoch(epoch, train_vec, valid_vec)`` is the logging hook.
+
+    Returns ``dict(train=[...], valid=[...], best_epoch, best_valid_loss, stopped)`` with the
+    per-epoch host loss vectors and ``stopped`` one of "patience", "max_iterations", "n_epochs".
+    Under data parallelism every rank sees the same validation vector and stops alike."""
+    rank, world = _rank_world()
+    model = trainer.model
+    save = exp_path is not None and rank == 0
+    if save:
+        os.makedirs(exp_path, exist_ok=True)
+    steps_per_epoch = len(epoch_order(len(train_store), batch_size, drop_last=True, rank=rank,
+                                      world_size=world))
+    hist = {"train": [], "valid": [], "best_epoch": None, "best_valid_loss": float("inf"),
+            "stopped": "n_epochs"}
+    global_step, stalled = 0, 0
+    for epoch in range(n_epochs):
+        train_vec = train_one_epoch(trainer, train_store, batch_size, extractor, shuffle=True,
+                                    generator=generator, drop_last=True, cached=cached)
+        if save:
+            torch.save(model.state_dict(), os.path.join(exp_path, "last_model.pth"))
+        valid_vec = valid_one_epoch(trainer, valid_store, batch_size, extractor, cached=cached)
+        hist["train"].append(train_vec)
+        hist["valid"].append(valid_vec)
+        if on_epoch is not None:
+            on_epoch(epoch, train_vec, valid_vec)
+        val = float(valid_vec[0])
+        if val < hist["best_valid_loss"]:
+            stalled = 0
+            hist["best_valid_loss"], hist["best_epoch"] = val, epoch
+            if save:
+                torch.save(model.state_dict(), os.path.join(exp_path, "best_model.pth"))
+        else:
+            stalled += 1
+            if stalled >= patience:
+                hist["stopped"] = "patience"
+                break
+        global_step += steps_per_epoch
+        if global_step >= max_iterations:
+            hist["stopped"] = "max_iterations"
+            break
+    return hist
 
 
 class GradBucketer:
@@ -254,6 +363,25 @@ class FusedTrainer:
                                  phon_len, self.weights)
         self.eng.backward(ctx, *grads)
         return loss
+
+    def eval_step(self, batch, intensity, mel_len_max=None, return_predictions=False):
+        """One validation batch (train.py:118-135): the eval-mode forward (no dropout, seed 0)
+        with the targets teacher-forced, then the forward-only fused loss.  Returns the 8-float
+        device loss vector, with ``return_predictions`` also the forward's 8-tuple.  Nothing of
+        the training state is touched -- the dropout seed, the gradient buffer, the optimizer,
+        the parameters, the captured step graphs -- and there is no host sync."""
+        (phoneme, spk_ids, phon_len, mel_tgt, pitch_tgt, energy_tgt, duration_tgt, mel_len) = batch[:8]
+        with torch.no_grad():
+            out, ctx = self.eng.forward(phoneme, spk_ids, duration_tgt, pitch_tgt, energy_tgt,
+                                        intensity=intensity, training=False, seed=0,
+                                        mel_len_max=mel_len_max if mel_len_max is not None
+                                        else mel_tgt.shape[1])
+            del ctx             # nothing runs backward: the saved activations go back at once
+            mel, post, pd, pp, avg_p, pe, avg_e, _ = out
+            loss, _ = fused_loss(mel, post, pd, pp.view(pd.shape), pe.view(pd.shape), mel_tgt,
+                                 duration_tgt, avg_p.view(pd.shape), avg_e.view(pd.shape),
+                                 mel_len, phon_len, self.weights, need_grads=False)
+        return (loss, out) if return_predictions else loss
 
     def apply(self):
         """Wait for the gradient all-reduce (stream-ordered) and run AdamW with the 1/N mean."""

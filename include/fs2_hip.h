@@ -364,6 +364,11 @@ typedef struct fs2_loss_desc {
 } fs2_loss_desc;
 int fs2_loss_fwd_bwd(const fs2_loss_desc* d, void* stream);
 int64_t fs2_loss_workspace_floats(int B, int Tm, int NM);
+/* The seven values and loss_out[7] alone (validation): the five d_* pointers are ignored and
+ * may be null, no gradient is computed or stored, and the workspace is the smaller
+ * fs2_loss_fwd_workspace_floats().  No float atomic: the values are reproducible bit for bit. */
+int fs2_loss_fwd(const fs2_loss_desc* d, void* stream);
+int64_t fs2_loss_fwd_workspace_floats(int B, int Tm, int NM);
 
 /* ------------------------------------------------------------------------------------------
  * Optimiser + weight preparation (K17; train.py:232 torch.optim.AdamW defaults).
