@@ -20,6 +20,11 @@ The log-mel front end (``emo_rank_tts/rank_model/audio_util.py::get_mel``), batc
 
     from fastspeech2 import MelFrontEnd, get_mel
 
+The prosody feature stage (``emo_rank_tts/rank_model/preprocess.py::feature_extraction``,
+:104-168): tracks, outlier-free statistics and finished items from the front end's output:
+
+    from fastspeech2 import ProsodyStage, extract_features, FeatureSet
+
 Compute runs only through libfs2_hip.so (include/fs2_hip.h); see DESIGN.md.
 """
 
@@ -31,7 +36,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 _RANK_DATASET = ("FineGrainedDataset", "RankGpuCollate", "RankDeviceStore")
 _AUDIO = ("MelFrontEnd", "get_mel")
-__all__ = ["load_config", *_RANK_DATASET, "FS2DeviceStore", *_AUDIO]
+_PROSODY = ("ProsodyStage", "extract_features", "FeatureSet")
+__all__ = ["load_config", *_RANK_DATASET, "FS2DeviceStore", *_AUDIO, *_PROSODY]
 
 
 def __getattr__(name):
@@ -45,6 +51,9 @@ def __getattr__(name):
     if name in _AUDIO:
         from . import audio
         return getattr(audio, name)
+    if name in _PROSODY:
+        from . import prosody
+        return getattr(prosody, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -185,6 +185,10 @@ SIGNATURES = {
     "fs2_mean3_leaky_relu": (I, [P, P, P, P, I64, Fl, I, P]),
     "fs2_melspec": (I, [P, P, I, P, P, P, P, I, I, I, I, I, I, I, P, P, P, P]),
     "fs2_energy_minmax": (I, [P, P, I, I, P, P]),
+    "fs2_prosody_track": (I, [P, I, P, P, P, P, P, I, I, I, I, P, P, P, P]),
+    "fs2_prosody_stats": (I, [P, P, P, P, I, P, P]),
+    "fs2_prosody_normalize": (I, [P, P, P, P, P, I, I, I, P, P, P, P]),
+    "fs2_prosody_minmax": (I, [P, P, P, P, I, P, P]),
     "fs2_fill": (I, [P, I64, Fl, I, P]),
     "fs2_add": (I, [P, P, I64, Fl, I, P]),
     "fs2_cast": (I, [P, I, P, I, I64, P]),

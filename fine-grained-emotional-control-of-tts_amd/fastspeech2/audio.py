@@ -18,8 +18,10 @@ All tables (window, twiddles, filterbank) are built here in float64 and rounded 
 the kernels (csrc/audio.hip: ``fs2_melspec``, ``fs2_energy_minmax``) use no transcendental but
 the final ``log``.  A batch is one upload and two launches, whatever the utterance lengths.
 
-Out of scope (they stay offline CPU preprocessing): MFA alignment, pyworld pitch, librosa
-loading / resampling, G2P.
+What follows it -- the cut to the alignment, pitch interpolation, phoneme averaging, the
+outlier-free statistics and the standardised items -- is fastspeech2/prosody.py.  Out of scope
+(they stay offline CPU preprocessing): MFA alignment, pyworld pitch, librosa loading /
+resampling, G2P.
 """
 
 import math

@@ -556,6 +556,35 @@ def energy_minmax(energy, mel_len, B, T_max, out):
          "fs2_energy_minmax")
 
 
+PROSODY_MAX_D = 4096                     # frames per utterance (csrc/prosody.hip PR_MAX_D)
+PROSODY_NONFINITE, PROSODY_UNVOICED, PROSODY_EMPTY = 1, 2, 4   # fs2_prosody_track status bits
+
+
+def prosody_track(src, src_start, src_len, dur, dur_off, trk_off, B, D_max, interpolate, average,
+                  track, ustat, status):
+    """src: float64 or float32 device tensor; the rest as include/fs2_hip.h names them"""
+    _chk(N.lib().fs2_prosody_track(_p(src), int(src.dtype == torch.float64), _p(src_start),
+                                   _p(src_len), _p(dur), _p(dur_off), _p(trk_off), B, D_max,
+                                   int(interpolate), int(average), _p(track), _p(ustat),
+                                   _p(status), _s()), "fs2_prosody_track")
+
+
+def prosody_stats(ustat, status, status2, group_off, G, gstat):
+    _chk(N.lib().fs2_prosody_stats(_p(ustat), _p(status), _p(status2), _p(group_off), G,
+                                   _p(gstat), _s()), "fs2_prosody_stats")
+
+
+def prosody_normalize(track, trk_off, status, status2, group_off, B, G, D_max, gstat, z, umm):
+    _chk(N.lib().fs2_prosody_normalize(_p(track), _p(trk_off), _p(status), _p(status2),
+                                       _p(group_off), B, G, D_max, _p(gstat), _p(z), _p(umm),
+                                       _s()), "fs2_prosody_normalize")
+
+
+def prosody_minmax(umm, status, status2, group_off, G, gstat):
+    _chk(N.lib().fs2_prosody_minmax(_p(umm), _p(status), _p(status2), _p(group_off), G,
+                                    _p(gstat), _s()), "fs2_prosody_minmax")
+
+
 def fill(X, n, value, *, dt):
     _chk(N.lib().fs2_fill(_p(X), n, value, dt, _s()), "fs2_fill")
 

@@ -645,6 +645,71 @@ int fs2_melspec(const float* wav, const int64_t* offsets, int B, const float* wi
 int fs2_energy_minmax(const float* energy, const int64_t* mel_len, int B, int T_max, float* out,
                       void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Prosody feature stage (rank_model/preprocess.py:104-168 feature_extraction with
+ * _average_by_duration :16-23, remove_outliers :27-31, normalize_field :35-46;
+ * fastspeech2/prosody.py drives it).  One field (pitch or energy) of B utterances in G groups
+ * takes the four launches below.  Every pointer is DEVICE memory; floats need 4-byte, doubles,
+ * int64 and the status words their own 8 / 8 / 4-byte alignment only.  No atomics and no
+ * workspace: two runs give the same bits.
+ *
+ * fs2_prosody_track: utterance b reads the values src[src_start[b] .. src_start[b] + D_b) of
+ * src (float64 when src_f64 != 0, else float32; src_start and src_len in elements, B int64
+ * each) and the durations dur[dur_off[b] .. dur_off[b+1]) (int64; dur_off B + 1 int64); a
+ * duration below 0 counts as 0 (the caller refuses those: the durations are on the device).
+ * D_b = min(sum of the durations, src_len[b], trk_off[b+1] - trk_off[b], D_max): nothing is read
+ * past an utterance's own src_len and nothing written past its own span of track.  The caller
+ * makes the four agree; where they do not, the frames of the span from D_b up to D_max are
+ * written as 0, so that fs2_prosody_normalize, which sees the span only, reads nothing that was
+ * not written.  In float64:
+ *   interpolate != 0 (pitch)  every frame equal to 0 becomes slope * (t - lo) + y_lo with
+ *     slope = (y_hi - y_lo) / (hi - lo) between its nearest non-zero neighbours lo < t < hi
+ *     (scipy interp1d's expression, each operation rounded once), the first / last non-zero
+ *     value before / after them; non-zero frames keep their value;
+ *   average != 0  every phoneme with a duration > 0 replaces its frames by their mean, summed
+ *     in float64 in frame order and rounded once to float32.
+ * track (float64, packed: utterance b at trk_off[b], trk_off B + 1 int64) receives the held
+ * values.  ustat (B, 5) float64 = n_clean, mean, M2, q1, q3: the quartiles of np.percentile(x,
+ * [25, 75]) (linear: virtual index (n - 1) q, a + (b - a) g, for g >= 0.5 b - (b - a) (1 - g)),
+ * and count, mean and sum of squared deviations of the values in [q1 - 1.5 iqr, q3 + 1.5 iqr],
+ * summed in a fixed order.  status[b] (int32) = 0, or FS2_PROSODY_NONFINITE (1, a NaN or
+ * infinity among the D_b values) | FS2_PROSODY_UNVOICED (2, interpolate and no non-zero frame) |
+ * FS2_PROSODY_EMPTY (4, D_b == 0); then track holds the values as read and ustat zeros.
+ * One workgroup per utterance, 8 * (D_max rounded up to a power of two) bytes of LDS.
+ *
+ * fs2_prosody_stats: utterances are ordered by group, group g the utterances group_off[g] ..
+ * group_off[g+1] - 1 (G + 1 int64).  gstat (G, 4) float64 = min, max, mean, std; this call
+ * writes mean and std: the triples of the utterances with status[u] | status2[u] == 0 (status2
+ * may be null: the other field's status words) merged in utterance order by Chan's update,
+ * std = sqrt(M2 / n), and 1 where var <= n eps var + (n mean eps)^2 (sklearn's constant
+ * feature) or the group has no such utterance (mean 0).
+ *
+ * fs2_prosody_normalize: z[trk_off[b] + t] = float32((track - mean_g) / std_g), one float64
+ * subtraction and division, rounded once; umm (B, 2) float64 = min and max of the float64
+ * quotient over the utterance.  An utterance with a status word set gets zeros and (+inf, -inf).
+ *
+ * fs2_prosody_minmax: writes min and max of gstat from umm over each group's utterances
+ * without a status word (+inf, -inf for none).
+ *
+ * Each returns 0 without a launch for B == 0 (G == 0 for the two per-group calls) and
+ * FS2_EINVAL, before any launch, for a null pointer (status2 excepted), B < 0, G < 0, D_max
+ * outside [1, 4096], or B > 0 with G < 1 in fs2_prosody_normalize.
+ * ------------------------------------------------------------------------------------------ */
+#define FS2_PROSODY_NONFINITE 1
+#define FS2_PROSODY_UNVOICED 2
+#define FS2_PROSODY_EMPTY 4
+int fs2_prosody_track(const void* src, int src_f64, const int64_t* src_start,
+                      const int64_t* src_len, const int64_t* dur, const int64_t* dur_off,
+                      const int64_t* trk_off, int B, int D_max, int interpolate, int average,
+                      double* track, double* ustat, int32_t* status, void* stream);
+int fs2_prosody_stats(const double* ustat, const int32_t* status, const int32_t* status2,
+                      const int64_t* group_off, int G, double* gstat, void* stream);
+int fs2_prosody_normalize(const double* track, const int64_t* trk_off, const int32_t* status,
+                          const int32_t* status2, const int64_t* group_off, int B, int G,
+                          int D_max, const double* gstat, float* z, double* umm, void* stream);
+int fs2_prosody_minmax(const double* umm, const int32_t* status, const int32_t* status2,
+                       const int64_t* group_off, int G, double* gstat, void* stream);
+
 /* utilities */
 int fs2_fill(void* X, int64_t n, float value, int dtype, void* stream);
 /* X[i] += alpha * Y[i] over n elements of dtype                                           */
